@@ -3,12 +3,18 @@
 Nesterov-SGD step) of the DOTA yolov7 KFIoU configuration at 800x800 (BASELINE.json config C4; at N=1 the same per-GPU
 workload), synthetic data of SURVEY.md §8(d), bf16 activations / fp32 accumulate / fp32 master weights.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...)
 
-Prints ONE JSON line on rank 0: metric/value (whole-job img/s, inputs resident in HBM), `roofline` for the dominant conv
-kernel (algorithmic FLOPs / HIP-event time of its launches inside the timed region, vs the dense bf16 MFMA peak), and
+Prints ONE JSON line on rank 0: metric/value (whole-job img/s, inputs resident in HBM) and ms_per_step of the K timed steps.
+A plain run does only that: set up, warm up, time the K steps, print.  `--full` adds everything else the line has carried:
+`roofline` for the dominant conv kernel (algorithmic FLOPs / HIP-event time of its launches in a second, instrumented pass of
+the K steps, vs the dense bf16 MFMA peak), the 8-image regime (`b8`), the loader-fed step, the inference and NMS blocks, and
 `cpu_baseline` (the torch-CPU oracle restatement timed on this host's cores on a bounded sample).
+
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (float32 / float64): the loss and its
+items, a fixed seeded sample of each head map and of the updated flat parameter buffer (at most ~20 MB in all).  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -164,6 +170,42 @@ def pmc_step_bytes(args):
     steps = doc.get("steps_profiled", 3)
     skip = ("nms_", "bitonic_", "compose_kernel", "topk_")         # the NMS timing block of this script, not part of a training step
     return int(sum(v["hbm_bytes_per_launch"] * v["launches"] for k, v in doc["kernels"].items() if not k.startswith(skip)) / steps)
+
+
+DUMP_SAMPLE = 1 << 20          # elements kept of each dumped array (a fixed seeded sample when the array is larger): <= 4 MB per file
+
+
+def _sample(t, seed, k=DUMP_SAMPLE):
+    """float32 host copy of `t` flattened: all of it when it has <= k elements, else k positions drawn from a generator seeded with
+    `seed` (sorted; the same positions for the same size on every run and every build)."""
+    import numpy as np
+    flat = t.detach().reshape(-1)
+    n = flat.numel()
+    if n > k:
+        idx = np.sort(np.random.default_rng(seed).integers(0, n, size=k))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def sample_outputs(last, params):
+    """What a caller of the timed step holds after its last call, as host arrays keyed by file name: the loss and its items (float64),
+    the head maps and the updated flat parameter buffer (float32, sampled by _sample)."""
+    import numpy as np
+    out = {"loss": last["loss"].detach().double().cpu().numpy().reshape(-1)}
+    for k, v in last["items"].items():
+        out[f"loss_{k}"] = torch.as_tensor(v).detach().double().cpu().numpy().reshape(-1)
+    for i, o in enumerate(last["outs"]):
+        out[f"head{i}"] = _sample(o, seed=1 + i)
+    out["params_after_step"] = _sample(params, seed=100)
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    return out
+
+
+def write_outputs(directory, arrays):
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in sorted(arrays.items()):
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def _cpu_baseline_worker(ver, mode, nc, size, threads, budget_s):
@@ -375,6 +417,11 @@ def main():
     ap.add_argument("--ver", default="yolov7")
     ap.add_argument("--mode", default="kfiou")
     ap.add_argument("--nc", type=int, default=16)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary blocks (kernel-timing pass + rooflines, b8, loader, inference, NMS, CPU baseline); "
+                         "the --no-* options below switch single blocks of a --full run off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, loss items, sampled head maps and updated weights) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-b8", action="store_true", help="skip the second regime (8 images per GPU)")
@@ -398,7 +445,9 @@ def main():
             port = sk.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-        os.execv(sys.executable, cmd)
+        import subprocess
+        sys.stdout.flush()
+        raise SystemExit(subprocess.call(cmd))         # a fresh child process (this one may already have opened the HIP runtime)
 
     import __graft_entry__ as ge
     from ryolov4_amd import parallel
@@ -442,18 +491,22 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(batch, steps, warmup, timing):
+    def measure(batch, steps, warmup, timing, capture=False):
         """One workload: `warmup` untimed steps, EXACTLY `steps` timed steps between barrier + synchronize, then (timing) the same
-        steps again with a HIP-event pair around every conv launch for the rooflines."""
+        steps again with a HIP-event pair around every conv launch for the rooflines.  `capture`: host copies of what the last timed
+        step returned (dump_outputs), taken right after the timed region, before any further step."""
         imgs, targets = synth_batch(batch, args.size, args.nc, args.mode == "csl", seed=42 + rank, per_image=64)
         imgs, targets = imgs.to(dev), targets.to(dev)          # inputs resident in HBM before the timed region
         dp.set_wire(parallel.pick_wire(batch, world, args.wire))
+        last = {}
 
-        def step():
+        def step(keep=False):
             outs = model(imgs, training=True)
-            loss, _ = crit(outs, targets, sync_items=False)
+            loss, items = crit(outs, targets, sync_items=False)
             loss.backward()                                   # engine backward + (N>1) RCCL all-reduce of the flat gradient buffer
             rt.sgd_step(lr, 0.937, grad_scale=dp.grad_scale, zero_grad=True)
+            if keep:                                          # the last timed step only: references, nothing copied or synchronized
+                last.update(outs=outs, loss=loss, items=items)
 
         def read_loss():                                      # one extra, untimed step whose loss is read back (host sync)
             outs = model(imgs, training=True)
@@ -470,12 +523,13 @@ def main():
         barrier()
         dp._reducer.collective_ms()                           # (drop the warm-up steps' stamps)
         t0 = time.perf_counter()
-        for _ in range(steps):
-            step()
+        for i in range(steps):
+            step(keep=capture and i == steps - 1)
         torch.cuda.synchronize()
         dt_rank = time.perf_counter() - t0                    # this rank's own K steps (before it waits for the others)
         barrier()
         dt = time.perf_counter() - t0
+        captured = sample_outputs(last, rt.flat) if capture and rank == 0 and last else None
         telemetry = None
         if world > 1:
             # clocks / power of this rank's GPU UNDER LOAD, outside the timed region: a few more steps are enqueued (asynchronously) and rocm-smi is
@@ -513,7 +567,7 @@ def main():
             per_rank = {"ms_per_step": [round(float(e[0]), 3) for e in every], "allreduce_ms_per_step": [round(float(e[1]), 3) for e in every],
                         "wire": dp.wire}
         return dict(dt=dt, dt_inst=dt_inst, timer=timer, loss_first=loss_first, loss_last=loss_last, batch=batch, steps=steps, per_rank=per_rank,
-                    telemetry=telemetry)
+                    telemetry=telemetry, captured=captured)
 
     def loader_fed(batch, steps, warmup, budget_frac=None, npool=256):
         """the SAME training step fed by the device-side loader instead of one resident synthetic batch.  A synthetic
@@ -682,8 +736,11 @@ def main():
                                                  "frac_chip_time = over seconds x CUs held / 256 (the side stream's kernels hold part of the chip)"}
         return res
 
+    full = args.full
     torch.cuda.reset_peak_memory_stats(dev)
-    m = measure(args.batch, args.steps, args.warmup, not args.no_kernel_timing)
+    m = measure(args.batch, args.steps, args.warmup, full and not args.no_kernel_timing, capture=args.dump_outputs is not None)
+    if m["captured"] is not None:
+        write_outputs(args.dump_outputs, m["captured"])
     g_main = rt.graph(args.batch, args.size, args.size, True)
     mem = {"peak_allocated_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 2),
            "plan_arena_gb": round(g_main.layout.total / 1e9, 2) if g_main.layout is not None else None,
@@ -692,10 +749,10 @@ def main():
                    "activations and activation gradients are liveness-placed slots of one arena (engine/arena.py)"}
     # second regime (VERDICT r1 #2 / SURVEY §8(d)): 8 images per GPU = the reference's nominal global batch 64 on 8 GPUs (train.py:150)
     m8 = None
-    if not args.no_b8 and args.batch != 8:
+    if full and not args.no_b8 and args.batch != 8:
         m8 = measure(8, 2 * args.steps, max(args.warmup, 5), not args.no_kernel_timing)
     fed = None
-    if not args.no_loader and (args.ver, args.mode) == ("yolov7", "kfiou"):
+    if full and not args.no_loader and (args.ver, args.mode) == ("yolov7", "kfiou"):
         fed = {"resident_pool": loader_fed(args.batch, args.steps, max(args.warmup, 5))}
         try:
             # a split four times larger (1024 images: a mosaic batch of 64 touches ~300 of them) under a budget of HALF its decoded size: every
@@ -793,12 +850,13 @@ def main():
                                      "on the loader's own stream under the previous step) from a synthetic 256-image 1024x1024 split; `value` above stays the "
                                      "synthetic resident-batch number; image decode is an array lookup here (no files on the GPU box)", **fed}
     # secondary metric of BASELINE.json: rotated-NMS latency at 10k boxes (device time; both sets, both thresholds, with and without the sort)
-    if world == 1 and not args.no_infer and (args.ver, args.mode) == ("yolov7", "kfiou"):
+    if full and world == 1 and not args.no_infer and (args.ver, args.mode) == ("yolov7", "kfiou"):
         out.update(infer_child(args))
-    out["nms"] = nms_block(dev)
-    out["nms_ms_10k_boxes"] = out["nms"]["mask_reduce_ms"]["C_0.65"]
-    out["nms_ms_10k_boxes_end_to_end_worst"] = max(out["nms"]["end_to_end_ms"].values())
-    if world == 1 and not args.no_cpu_baseline:
+    if full:
+        out["nms"] = nms_block(dev)
+        out["nms_ms_10k_boxes"] = out["nms"]["mask_reduce_ms"]["C_0.65"]
+        out["nms_ms_10k_boxes_end_to_end_worst"] = max(out["nms"]["end_to_end_ms"].values())
+    if full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
     print(json.dumps(out))
 

@@ -15,7 +15,7 @@ def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline():
     import torch
     gc.collect()
     torch.cuda.empty_cache()
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "16", "--size", "256"],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "16", "--size", "256", "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -51,8 +51,34 @@ def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline():
     assert d["nms_ms_10k_boxes"] == nms["mask_reduce_ms"]["C_0.65"]
 
 
+def test_plain_bench_times_only_the_steps_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline figures only (no instrumented pass, no secondary blocks); --dump-outputs writes the
+    last timed step's loss, loss items, sampled head maps and updated weights as float32 / float64 .npy files."""
+    import numpy as np
+    import torch
+    gc.collect()
+    torch.cuda.empty_cache()
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8", "--size", "256",
+                        "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "img/s" and d["dtype"] == "bf16" and d["higher_is_better"] is True
+    assert abs(d["value"] - 8 / (d["ms_per_step"] / 1e3)) < 1e-2 * d["value"]
+    for k in ("roofline", "kernel_timing", "b8", "loader_fed", "infer_c5", "nms", "cpu_baseline"):
+        assert k not in d, k
+    files = {p.name: np.load(p) for p in out.iterdir()}
+    assert {"loss.npy", "loss_total_loss.npy", "head0.npy", "head1.npy", "head2.npy", "params_after_step.npy"} <= set(files), sorted(files)
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 * 2 ** 20
+    for name, a in files.items():
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all(), name
+    assert abs(float(files["loss.npy"][0]) - float(files["loss_total_loss.npy"][0])) <= 1e-6 * abs(float(files["loss.npy"][0])) + 1e-6
+
+
 def test_bench_gpus_2_launches_two_ranks_by_itself():
-    """`python bench.py --gpus 2` WITHOUT a launcher must re-exec under torch.distributed.run (never report a single rank as n_gpus 2):
+    """`python bench.py --gpus 2` WITHOUT a launcher must start itself under torch.distributed.run (never report a single rank as n_gpus 2):
     two ranks over gloo on the one GPU of the test box, overlapped bucketed all-reduce of the flat gradient buffer, replicas compared
     bit for bit after the steps (train.py:150-152,198-202)."""
     import torch

@@ -13,11 +13,11 @@ cp gpurun_out/${TAG}_pmc_step_traffic.json profiles/${TAG}_pmc_step_traffic.json
 timeout 1500 bash tools/pmc_step_mfma.sh $TAG > $O/pmc_step_mfma.txt 2>&1
 cp gpurun_out/${TAG}_pmc_step_mfma_busy.json profiles/${TAG}_pmc_step_mfma_busy.json
 # 2. default bench line
-( time timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_time.txt
+( time timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_time.txt
 # 3. rocprofv3 kernel stats, serialized streams, b64 and b8
 cd /tmp; export TMPDIR=/tmp
-RYOLO_WGRAD_STREAM=0 RYOLO_FWD_FORK=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_b64 -o run -- python $R/bench.py --no-cpu-baseline --no-loader --no-b8 --steps 8 > $O/prof_b64.json 2> $O/prof_b64.err
-RYOLO_WGRAD_STREAM=0 RYOLO_FWD_FORK=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_b8 -o run -- python $R/bench.py --no-cpu-baseline --no-loader --no-b8 --batch 8 --steps 20 > $O/prof_b8.json 2> $O/prof_b8.err
+RYOLO_WGRAD_STREAM=0 RYOLO_FWD_FORK=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_b64 -o run -- python $R/bench.py --full --no-cpu-baseline --no-loader --no-b8 --steps 8 > $O/prof_b64.json 2> $O/prof_b64.err
+RYOLO_WGRAD_STREAM=0 RYOLO_FWD_FORK=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_b8 -o run -- python $R/bench.py --full --no-cpu-baseline --no-loader --no-b8 --batch 8 --steps 20 > $O/prof_b8.json 2> $O/prof_b8.err
 cd $R
 # 4. per-launch tables
 B=64 TOP=400 RYOLO_WGRAD_STREAM=0 RYOLO_FWD_FORK=0 timeout 600 python tools/profile_layers.py > $O/per_launch_b64.txt 2>&1
@@ -54,8 +54,8 @@ B=64 SZ=800 timeout 300 python tools/profile_infer_layers.py > $O/infer_layers_b
 B=8 SZ=1024 timeout 300 python tools/profile_infer_layers.py > $O/infer_layers_b8_1024.txt 2>&1
 B=8 K=40 timeout 300 python tools/bench_graph_step.py > $O/graph_step_b8.txt 2>&1
 # 6. other configs + batch sweep
-for cfg in "yolov4 kfiou 608 2" "yolov7 csl 800 16" "yolov5 kfiou 800 16"; do set -- $cfg; timeout 300 python bench.py --ver $1 --mode $2 --size $3 --nc $4 --no-cpu-baseline --no-loader --no-b8 --steps 8 > $O/cfg_$1_$2.json 2> $O/cfg_$1_$2.err; done
-for b in 96 128; do timeout 300 python bench.py --batch $b --no-cpu-baseline --no-loader --no-b8 --no-kernel-timing --steps 8 > $O/batch$b.json 2> $O/batch$b.err; done
+for cfg in "yolov4 kfiou 608 2" "yolov7 csl 800 16" "yolov5 kfiou 800 16"; do set -- $cfg; timeout 300 python bench.py --full --ver $1 --mode $2 --size $3 --nc $4 --no-cpu-baseline --no-loader --no-b8 --steps 8 > $O/cfg_$1_$2.json 2> $O/cfg_$1_$2.err; done
+for b in 96 128; do timeout 300 python bench.py --full --batch $b --no-cpu-baseline --no-loader --no-b8 --no-kernel-timing --steps 8 > $O/batch$b.json 2> $O/batch$b.err; done
 # 7. overfit curves
 timeout 600 python tools/overfit_curve.py kfiou 300 > $O/overfit_kfiou.json 2> $O/overfit_kfiou.err
 timeout 600 python tools/overfit_curve.py csl 300 > $O/overfit_csl.json 2> $O/overfit_csl.err
