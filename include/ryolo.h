@@ -327,6 +327,31 @@ int ryolo_polys_to_xywha(const float* polys, int64_t n, float* out, ryolo_stream
 int ryolo_dets_to_polys(float* dets, const int* img_of_det, const int* shapes, int current_dim, int rescale, int64_t n, float* polys,
                         ryolo_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Full-scene (tiled) detection (csrc/tiled.hip; lib/tiled.py).  The reference detects on offline-cut patches only (data/DOTA.yaml,
+ * detect.py letterboxes a whole file to img_size); these stages cut a scene into overlapping windows, feed them group by group to the
+ * captured forward + post_process, and merge the per-window detections in scene coordinates with class-wise rotated NMS on the device.
+ * A scene of T windows in groups of B: T_pad = ceil(T / B) * B, candidate slot of detection j of window w = w * mk + j, ld = T_pad * mk.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* windows win0 .. win0 + count - 1 of the table win int64 [nwin][5] = (byte offset of the window's source image from pool, its height,
+ * width, window origin x0, y0) -> dst fp32 [>= count, 3, S, S] slots 0 .. count - 1 as RGB / 255 (114 / 255 outside the source image);
+ * later slots are not touched.  S % 4 == 0.  Bit-identical to ryolo_paste_rects(fill = 114) + ryolo_to_tensor. */
+int ryolo_tile_cut(const uint8_t* pool, const int64_t* win, int64_t win0, int count, int S, float* dst, ryolo_stream_t stream);
+/* one group's post_process output dets [batch, mk, 7] / num [batch] (windows win0 .. win0 + batch - 1 of a scene of nwin windows;
+ * geom fp32 [nwin][3] = (x0, y0, rate)) -> cand [ld][7] rows (x + x0) / rate, (y + y0) / rate, w / rate, h / rate, theta, score, cls
+ * at slot (win0 + b) * mk + j, key [nc][ld] = score in the row of the class, -inf in the others, fkey [ld] = -inf.  Slots past num[b]
+ * and windows at or past nwin: zero rows, -inf keys.  (win0 + batch) * mk <= ld. */
+int ryolo_tile_collect(const float* dets, const int32_t* num, int batch, int64_t mk, const float* geom, int64_t win0, int64_t nwin, int nc,
+                       int64_t ld, float* cand, float* key, float* fkey, ryolo_stream_t stream);
+/* skey / order [nc, K] = ryolo_topk_desc of key -> rboxes [nc, K, 5] = (x, y, w, h, theta degrees) of the selected candidates in scene
+ * pixels, no class offset (zero rows for -inf entries): the input of ryolo_nms_rotated_batched with batch = nc. */
+int ryolo_tile_merge_gather(const float* cand, const float* skey, const int64_t* order, int nc, int64_t K, float* rboxes, ryolo_stream_t stream);
+/* kept positions keep [nc, keep_stride] / num_keep [nc] of that NMS -> fkey[order[c, keep[c, j]]] = skey[c, keep[c, j]] */
+int ryolo_tile_mark(const float* skey, const int64_t* order, const int64_t* keep, const int32_t* num_keep, int nc, int64_t K,
+                    int64_t keep_stride, float* fkey, ryolo_stream_t stream);
+/* order [>= num[0]] = ryolo_topk_desc of fkey, num [1] its selection count -> out [max_det, 7] = cand[order[j]] for j < num[0], zeros after */
+int ryolo_tile_emit(const float* cand, const int64_t* order, const int32_t* num, int64_t max_det, float* out, ryolo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

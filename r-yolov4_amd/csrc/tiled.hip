@@ -1,0 +1,191 @@
+// Full-scene (tiled) detection for gfx950: a scene far larger than the network input is cut into overlapping windows, every group of
+// windows goes through the captured forward + post_process (Yolo.capture_inference(..., post=...)), and the per-window detections are
+// merged back in scene coordinates with CLASS-WISE rotated NMS — all on the device, no host read between groups (lib/tiled.py).
+//
+//   tile_cut_kernel      uint8 HWC BGR scene (pool base + byte offset) -> the graph's static input fp32 [B,3,S,S] as RGB / 255, 114 / 255
+//                        outside the scene; one launch per window group.  Bit-identical to ryolo_paste_rects(fill=114) + ryolo_to_tensor
+//                        (the chain it replaces) without their intermediate canvas.
+//   tile_collect_kernel  dets [B,mk,7] / num [B] of a group -> candidate rows in scene coordinates at the fixed slot window * mk + j and the
+//                        per-class key rows key [nc][ld] (score in the row of the box's class, -inf elsewhere); every slot of the group is
+//                        written exactly once (no fill pass, no atomics: deterministic).
+//   (ryolo_topk_desc over the nc key rows)
+//   tile_gather_kernel   per-class top-K slots -> NMS boxes [nc,K,5] in scene pixels, theta in degrees, NO class offset: the per-image path
+//                        separates classes by cls * 4096 px (lib/general.py:14), which collides on scenes wider than 4096 px; here a
+//                        class is its own NMS batch row (ryolo_nms_rotated_batched with batch = nc).
+//   tile_mark_kernel     kept entries -> final key [ld] by slot (the collect pass reset it to -inf)
+//   (ryolo_topk_desc over the final key: score desc, slot asc, capped at max_det)
+//   tile_emit_kernel     out [max_det,7] = candidate rows in that order, zero padded.
+// Compiled with -ffp-contract=off: the coordinate mapping (x + x0) / rate is restated bit for bit by numpy in the tests.
+#include "common.h"
+
+// window table rows (int64 [nwin][5]): byte offset of the window's source image from `pool`, its height, width, window origin x0, y0
+#define TW_ROW 5
+
+// One thread = 4 consecutive output pixels of one window row (S % 4 == 0): 12 source bytes, one float4 per colour plane.
+__global__ __launch_bounds__(256) void tile_cut_kernel(const uint8_t* __restrict__ pool, const int64_t* __restrict__ win, int S,
+                                                       float* __restrict__ dst)
+{
+    const int w = blockIdx.y;
+    const int sq = S >> 2;
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= (int64_t)S * sq) return;
+    const int y = (int)(q / sq);
+    const int x = (int)(q - (int64_t)y * sq) * 4;
+    const int64_t* t = win + (int64_t)w * TW_ROW;
+    const int64_t off = t[0];
+    const int H = (int)t[1], W = (int)t[2];
+    const int sy = (int)t[4] + y, sx = (int)t[3] + x;
+    uint8_t px[12];
+    if (sy < H && sx + 4 <= W) {
+        __builtin_memcpy(px, pool + off + ((int64_t)sy * W + sx) * 3, 12);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            px[3 * k] = px[3 * k + 1] = px[3 * k + 2] = (uint8_t)114;
+            if (sy < H && sx + k < W) {
+                const uint8_t* sp = pool + off + ((int64_t)sy * W + sx + k) * 3;
+                px[3 * k] = sp[0]; px[3 * k + 1] = sp[1]; px[3 * k + 2] = sp[2];
+            }
+        }
+    }
+    const int64_t plane = (int64_t)S * S;
+    float* o = dst + (int64_t)w * 3 * plane + (int64_t)y * S + x;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {                                       // BGR -> RGB, .float() / 255 (ryolo_to_tensor's expression)
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) v[k] = (float)px[k * 3 + (2 - c)] / 255.0f;
+        *reinterpret_cast<float4*>(o + c * plane) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
+
+// One thread = one detection slot j of window b of the group (global window win0 + b).
+__global__ __launch_bounds__(256) void tile_collect_kernel(const float* __restrict__ dets, const int32_t* __restrict__ num, int64_t mk,
+                                                           const float* __restrict__ geom, int64_t win0, int64_t nwin, int nc, int64_t ld,
+                                                           float* __restrict__ cand, float* __restrict__ key, float* __restrict__ fkey)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = blockIdx.y;
+    if (j >= mk) return;
+    const int64_t wg = win0 + b;
+    const int64_t slot = wg * mk + j;
+    float* c = cand + slot * 7;
+    float s = -INFINITY;
+    int cls = -1;
+    if (wg < nwin && j < (int64_t)num[b]) {
+        const float* d = dets + ((int64_t)b * mk + j) * 7;
+        const float* g = geom + wg * 3;
+        const float x0 = g[0], y0 = g[1], rate = g[2];
+        c[0] = (d[0] + x0) / rate;
+        c[1] = (d[1] + y0) / rate;
+        c[2] = d[2] / rate;
+        c[3] = d[3] / rate;
+        c[4] = d[4]; c[5] = d[5]; c[6] = d[6];
+        s = d[5];
+        cls = (int)d[6];
+    } else {
+        for (int t = 0; t < 7; t++) c[t] = 0.f;
+    }
+    for (int k = 0; k < nc; k++) key[(int64_t)k * ld + slot] = k == cls ? s : -INFINITY;
+    fkey[slot] = -INFINITY;
+}
+
+__global__ __launch_bounds__(256) void tile_gather_kernel(const float* __restrict__ cand, const float* __restrict__ skey,
+                                                          const int64_t* __restrict__ order, int64_t K, float* __restrict__ rboxes)
+{
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int c = blockIdx.y;
+    if (k >= K) return;
+    const int64_t e = (int64_t)c * K + k;
+    float* r = rboxes + e * 5;
+    if (!(skey[e] > -INFINITY)) {
+        for (int t = 0; t < 5; t++) r[t] = 0.f;
+        return;
+    }
+    const float* p = cand + order[e] * 7;
+    r[0] = p[0]; r[1] = p[1]; r[2] = p[2]; r[3] = p[3];
+    r[4] = p[4] / 3.14159265358979323846f * 180.f;                     // pp_gather_kernel's rad -> deg
+}
+
+__global__ __launch_bounds__(256) void tile_mark_kernel(const float* __restrict__ skey, const int64_t* __restrict__ order,
+                                                        const int64_t* __restrict__ keep, const int32_t* __restrict__ num_keep, int64_t K,
+                                                        int64_t keep_stride, float* __restrict__ fkey)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int c = blockIdx.y;
+    if (j >= keep_stride || j >= (int64_t)num_keep[c]) return;
+    const int64_t e = (int64_t)c * K + keep[(int64_t)c * keep_stride + j];
+    fkey[order[e]] = skey[e];                                          // a slot belongs to one class row: no two threads share it
+}
+
+__global__ __launch_bounds__(256) void tile_emit_kernel(const float* __restrict__ cand, const int64_t* __restrict__ order,
+                                                        const int32_t* __restrict__ num, int64_t max_det, float* __restrict__ out)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= max_det) return;
+    float* o = out + j * 7;
+    if (j < (int64_t)num[0]) {
+        const float* p = cand + order[j] * 7;
+        for (int t = 0; t < 7; t++) o[t] = p[t];
+    } else {
+        for (int t = 0; t < 7; t++) o[t] = 0.f;
+    }
+}
+
+extern "C" int ryolo_tile_cut(const uint8_t* pool, const int64_t* win, int64_t win0, int count, int S, float* dst, hipStream_t stream)
+{
+    if (count < 0 || win0 < 0 || S <= 0) return RY_ERR_ARG;
+    if (S % 4 != 0 || count > 65535) return RY_ERR_UNSUPPORTED;
+    if (count == 0) return RY_OK;
+    if (!pool || !win || !dst) return RY_ERR_ARG;
+    hipLaunchKernelGGL(tile_cut_kernel, dim3((unsigned)ry_cdiv((int64_t)S * (S / 4), 256), count), dim3(256), 0, stream, pool,
+                       win + win0 * TW_ROW, S, dst);
+    RY_CHECK_LAUNCH();
+    return RY_OK;
+}
+
+extern "C" int ryolo_tile_collect(const float* dets, const int32_t* num, int batch, int64_t mk, const float* geom, int64_t win0, int64_t nwin,
+                                  int nc, int64_t ld, float* cand, float* key, float* fkey, hipStream_t stream)
+{
+    if (batch < 0 || mk < 0 || win0 < 0 || nwin < 0 || nc < 0 || ld < 0) return RY_ERR_ARG;
+    if ((win0 + batch) * mk > ld || batch > 65535) return RY_ERR_ARG;      // every slot of the group lies inside the candidate rows
+    if (batch == 0 || mk == 0) return RY_OK;
+    if (!dets || !num || !geom || !cand || !fkey || (nc && !key)) return RY_ERR_ARG;
+    hipLaunchKernelGGL(tile_collect_kernel, dim3((unsigned)ry_cdiv(mk, 256), batch), dim3(256), 0, stream, dets, num, mk, geom, win0, nwin, nc,
+                       ld, cand, key, fkey);
+    RY_CHECK_LAUNCH();
+    return RY_OK;
+}
+
+extern "C" int ryolo_tile_merge_gather(const float* cand, const float* skey, const int64_t* order, int nc, int64_t K, float* rboxes,
+                                       hipStream_t stream)
+{
+    if (nc < 0 || K < 0 || nc > 65535) return RY_ERR_ARG;
+    if (nc == 0 || K == 0) return RY_OK;
+    if (!cand || !skey || !order || !rboxes) return RY_ERR_ARG;
+    hipLaunchKernelGGL(tile_gather_kernel, dim3((unsigned)ry_cdiv(K, 256), nc), dim3(256), 0, stream, cand, skey, order, K, rboxes);
+    RY_CHECK_LAUNCH();
+    return RY_OK;
+}
+
+extern "C" int ryolo_tile_mark(const float* skey, const int64_t* order, const int64_t* keep, const int32_t* num_keep, int nc, int64_t K,
+                               int64_t keep_stride, float* fkey, hipStream_t stream)
+{
+    if (nc < 0 || K < 0 || keep_stride < 0 || keep_stride > K || nc > 65535) return RY_ERR_ARG;
+    if (nc == 0 || keep_stride == 0) return RY_OK;
+    if (!skey || !order || !keep || !num_keep || !fkey) return RY_ERR_ARG;
+    hipLaunchKernelGGL(tile_mark_kernel, dim3((unsigned)ry_cdiv(keep_stride, 256), nc), dim3(256), 0, stream, skey, order, keep, num_keep, K,
+                       keep_stride, fkey);
+    RY_CHECK_LAUNCH();
+    return RY_OK;
+}
+
+extern "C" int ryolo_tile_emit(const float* cand, const int64_t* order, const int32_t* num, int64_t max_det, float* out, hipStream_t stream)
+{
+    if (max_det < 0) return RY_ERR_ARG;
+    if (max_det == 0) return RY_OK;
+    if (!cand || !order || !num || !out) return RY_ERR_ARG;
+    hipLaunchKernelGGL(tile_emit_kernel, dim3((unsigned)ry_cdiv(max_det, 256)), dim3(256), 0, stream, cand, order, num, max_det, out);
+    RY_CHECK_LAUNCH();
+    return RY_OK;
+}

@@ -1,0 +1,325 @@
+"""Full-scene detection: a scene far larger than the network input (DOTA scenes run to thousands of pixels per side) is cut into overlapping
+windows at the network size, every group of windows runs through ONE captured graph (Yolo.capture_inference(batch, size, post=...): the
+forward, the decode and post_process), and the per-window detections are mapped back to scene pixels and merged with class-wise rotated
+NMS — the workflow users of the reference rebuild by hand around detect.py, which only letterboxes a whole file to img_size.
+
+    tile_plan(H, W, size, overlap, rates=(1.0,)) -> [(rate_index, x0, y0)]        the window table (host, pure Python)
+    TiledDetector(model, size, overlap, batch, ...)(scene) -> Tensor[n, 7]          (x, y, w, h, theta_rad, score, cls) in scene pixels
+    TiledDetector.run_async(scene) -> (out [max_det, 7], num [1] int32)             the same with the count left on the device
+    TiledDetector.detect_files(paths) -> iterator of (path, Tensor[n, 7])           scene i + 1 decoded / uploaded while scene i runs
+    write_dota_task1({name: dets}, out_dir, class_names)                            DOTA Task1 files (Task1_<class>.txt)
+
+Device side (csrc/tiled.hip): per group ryolo_tile_cut (scene -> the graph's static input), the graph replay, ryolo_tile_collect (scene
+rows at the fixed slot window * mk + j, per-class keys); then per scene ryolo_topk_desc over the nc class rows, ryolo_tile_merge_gather,
+ryolo_nms_rotated_batched with batch = nc (no cls * 4096 offset: post_process's class separation collides on scenes wider than 4096 px),
+ryolo_tile_mark, ryolo_topk_desc over the kept entries (score desc, slot asc) and ryolo_tile_emit.  No allocation and no host read after the
+scene's upload; __call__ reads one count per scene.
+"""
+import math
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+from .. import hip
+from ..datasets import augment as A
+from . import general
+
+_SORT_MAX = 16384            # ryolo_topk_desc selects at most this many entries per row
+
+
+# ------------------------------------------------------------------------------------------ window plan
+def resized_extent(H, W, rate):
+    """(h, w) of the scene resized by `rate`."""
+    return int(H * rate + 0.5), int(W * rate + 0.5)
+
+
+def _starts(L, size, stride):
+    if L <= size:
+        return [0]
+    out, x = [], 0
+    while x + size < L:
+        out.append(x)
+        x += stride
+    out.append(L - size)
+    return out
+
+
+def tile_plan(H, W, size, overlap, rates=(1.0,)):
+    """Windows of an H x W scene: [(rate_index, x0, y0)], row-major by rate, then y0, then x0 (this order fixes the tie-breaks of the
+    merge).  Per rate the scene is resized to resized_extent(H, W, rate); along an axis of length L the starts are 0, stride, 2 * stride,
+    ... (stride = size - overlap) up to the first start x with x + size >= L, which becomes L - size; an axis no longer than `size` has
+    the single start 0 (the window reaches past the scene and is filled with 114 grey)."""
+    if not isinstance(size, (int, np.integer)) or size <= 0 or size % 32:
+        raise ValueError(f"tile_plan: size must be a positive multiple of 32 (the largest head stride), got {size}")
+    if not isinstance(overlap, (int, np.integer)) or not 0 <= overlap < size:
+        raise ValueError(f"tile_plan: overlap must satisfy 0 <= overlap < size, got {overlap}")
+    rates = tuple(rates)
+    if not rates or any(not (float(r) > 0) or not math.isfinite(float(r)) for r in rates):
+        raise ValueError(f"tile_plan: rates must be positive, got {rates}")
+    if int(H) <= 0 or int(W) <= 0:
+        raise ValueError(f"tile_plan: empty scene {H} x {W}")
+    stride = size - overlap
+    out = []
+    for ri, r in enumerate(rates):
+        h, w = resized_extent(H, W, float(r))
+        if h <= 0 or w <= 0:
+            raise ValueError(f"tile_plan: rate {r} leaves nothing of a {H} x {W} scene")
+        xs = _starts(w, size, stride)
+        for y0 in _starts(h, size, stride):
+            out.extend((ri, x0, y0) for x0 in xs)
+    return out
+
+
+# ------------------------------------------------------------------------------------------ per-scene-shape buffers
+def _h2d(dst, arr):
+    """Small host table -> existing device tensor through pinned memory, non-blocking on the current stream."""
+    stage = torch.empty(dst.shape, dtype=dst.dtype, pin_memory=True)
+    stage.numpy()[...] = arr
+    dst.copy_(stage, non_blocking=True)
+
+
+class ScenePlan:
+    """Static buffers of one (H, W, rates): window table, candidate rows, class keys, merge and final-order buffers, resized copies.
+    `det` supplies device, batch, mk (detection rows per window), nc, size, overlap, rates, max_nms and max_det (a TiledDetector)."""
+
+    def __init__(self, det, H, W):
+        dev, B, mk, nc, S = det.device, det.batch, det.mk, det.nc, det.size
+        self.H, self.W = H, W
+        self.batch, self.mk, self.nc, self.max_det = B, mk, nc, det.max_det
+        self.windows = tile_plan(H, W, S, det.overlap, det.rates)
+        self.extents = [resized_extent(H, W, r) for r in det.rates]
+        T = self.T = len(self.windows)
+        self.groups = (T + B - 1) // B
+        ld = self.ld = self.groups * B * mk
+        f32, i32, i64 = torch.float32, torch.int32, torch.int64
+        wa = np.asarray(self.windows, dtype=np.int64).reshape(-1, 3)
+        ext = np.asarray(self.extents, dtype=np.int64)
+        self.rows = np.stack([np.zeros(T, np.int64), ext[wa[:, 0], 0], ext[wa[:, 0], 1], wa[:, 1], wa[:, 2]], 1)   # src_off set per scene
+        self.rate_of = wa[:, 0]
+        self.win = torch.empty((T, 5), dtype=i64, device=dev)
+        self.geom = torch.empty((T, 3), dtype=f32, device=dev)
+        _h2d(self.geom, np.stack([wa[:, 1], wa[:, 2], np.asarray(det.rates, np.float32)[wa[:, 0]]], 1).astype(np.float32))
+        # resized copies of the scene (rates != 1), one staging buffer
+        self.stage_off, total = [], 0
+        for r, (h, w) in zip(det.rates, self.extents):
+            self.stage_off.append(total if r != 1.0 else None)
+            if r != 1.0:
+                total += ((h * w * 3 + 15) // 16) * 16
+        self.stage = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+        self.resize_items = [(ri, h, w) for ri, (r, (h, w)) in enumerate(zip(det.rates, self.extents)) if r != 1.0]
+        # candidates and keys: every slot is written by ryolo_tile_collect
+        self.cand = torch.empty((ld, 7), dtype=f32, device=dev)
+        self.key = torch.empty((nc, ld), dtype=f32, device=dev)
+        self.fkey = torch.empty(ld, dtype=f32, device=dev)
+        self.Kc, self.Kf = min(det.max_nms, ld), min(det.max_det, ld)
+        need, need2 = hip._Z(), hip._Z()
+        hip.call("ryolo_sort_workspace_bytes", nc, self.Kc, need)
+        hip.call("ryolo_sort_workspace_bytes", 1, self.Kf, need2)
+        self.sort_ws = torch.empty(max(need.value, need2.value, 16), dtype=torch.uint8, device=dev)
+        self.skey = torch.empty((nc, self.Kc), dtype=f32, device=dev)
+        self.order = torch.empty((nc, self.Kc), dtype=i64, device=dev)
+        self.nsel = torch.empty(nc, dtype=i32, device=dev)
+        self.rboxes = torch.empty((nc, self.Kc, 5), dtype=f32, device=dev)
+        hip.call("ryolo_nms_workspace_bytes", nc, self.Kc, need)
+        self.nms_ws = torch.empty(max(need.value, 16), dtype=torch.uint8, device=dev)
+        self.keep = torch.empty((nc, self.Kc), dtype=i64, device=dev)
+        self.nkeep = torch.empty(nc, dtype=i32, device=dev)
+        self.fskey = torch.empty((1, self.Kf), dtype=f32, device=dev)
+        self.forder = torch.empty((1, self.Kf), dtype=i64, device=dev)
+        self.num = torch.empty(1, dtype=i32, device=dev)
+        self.out = torch.empty((self.max_det, 7), dtype=f32, device=dev)
+
+    def collect(self, dets, num, g):
+        """Group g's post_process output dets [batch, mk, 7] / num [batch] -> candidate rows and class keys of its slots."""
+        B = self.batch
+        hip.call("ryolo_tile_collect", hip.ptr(dets), hip.ptr(num), B, self.mk, hip.ptr(self.geom), g * B, self.T, self.nc, self.ld,
+                 hip.ptr(self.cand), hip.ptr(self.key), hip.ptr(self.fkey), hip.stream())
+
+    def merge(self, merge_iou, gt_only=True):
+        """Class-wise rotated NMS over every collected candidate, then the final order -> (out [max_det, 7], num [1]) on the device."""
+        nc, Kc, Kf, st = self.nc, self.Kc, self.Kf, hip.stream()
+        hip.call("ryolo_topk_desc", hip.ptr(self.key), nc, self.ld, Kc, hip.ptr(self.skey), hip.ptr(self.order), hip.ptr(self.nsel), hip.ptr(self.sort_ws),
+                 self.sort_ws.numel(), st)
+        hip.call("ryolo_tile_merge_gather", hip.ptr(self.cand), hip.ptr(self.skey), hip.ptr(self.order), nc, Kc, hip.ptr(self.rboxes), st)
+        hip.call("ryolo_nms_rotated_batched", hip.ptr(self.rboxes), hip.ptr(self.nsel), nc, Kc, merge_iou, 1 if gt_only else 0, Kc,
+                 hip.ptr(self.nms_ws), self.nms_ws.numel(), hip.ptr(self.keep), Kc, hip.ptr(self.nkeep), st)
+        hip.call("ryolo_tile_mark", hip.ptr(self.skey), hip.ptr(self.order), hip.ptr(self.keep), hip.ptr(self.nkeep), nc, Kc, Kc, hip.ptr(self.fkey), st)
+        hip.call("ryolo_topk_desc", hip.ptr(self.fkey), 1, self.ld, Kf, hip.ptr(self.fskey), hip.ptr(self.forder), hip.ptr(self.num), hip.ptr(self.sort_ws),
+                 self.sort_ws.numel(), st)
+        hip.call("ryolo_tile_emit", hip.ptr(self.cand), hip.ptr(self.forder), hip.ptr(self.num), self.max_det, hip.ptr(self.out), st)
+        return self.out, self.num
+
+
+class _Placed:
+    """A scene resident on the device: `base` tensor + byte offset (what the table-driven kernels take), and the object that owns it."""
+
+    def __init__(self, base, off, H, W, owner):
+        self.base, self.off, self.H, self.W, self.owner = base, off, H, W, owner
+
+    @property
+    def addr(self):
+        return self.base.data_ptr() + self.off
+
+
+# ------------------------------------------------------------------------------------------ detector
+class TiledDetector:
+    """Detect on full scenes with one captured graph of an eval-mode Yolo (see the module docstring).
+
+    conf_thres / iou_thres: post_process of every window (captured with the graph).  merge_iou (default iou_thres) and gt_only: the
+    class-wise rotated NMS of the merge.  rates: the scene is resized once per rate (INTER_AREA below 1, INTER_LINEAR above; rate 1 is cut
+    straight from the scene) and every resized copy is tiled; boxes are mapped back to the original scene.  max_nms: candidates per class
+    entering the merge; max_det: detections per scene."""
+
+    def __init__(self, model, size=1024, overlap=200, batch=8, conf_thres=0.1, iou_thres=0.4, merge_iou=None, rates=(1.0,), max_nms=5000,
+                 max_det=5000, gt_only=True):
+        rates = tuple(float(r) for r in rates)
+        tile_plan(size, size, size, overlap, rates)                      # argument validation
+        if int(batch) < 1:
+            raise ValueError(f"TiledDetector: batch must be >= 1, got {batch}")
+        for name, v in (("max_nms", max_nms), ("max_det", max_det)):
+            if not 1 <= int(v) <= _SORT_MAX:
+                raise ValueError(f"TiledDetector: {name} must lie in [1, {_SORT_MAX}], got {v}")
+        if model.training:
+            raise RuntimeError("TiledDetector: call model.eval() first")
+        self.size, self.overlap, self.batch, self.rates = int(size), int(overlap), int(batch), rates
+        self.conf_thres, self.iou_thres = float(conf_thres), float(iou_thres)
+        self.merge_iou = self.iou_thres if merge_iou is None else float(merge_iou)
+        self.max_nms, self.max_det, self.gt_only = int(max_nms), int(max_det), bool(gt_only)
+        # the graph replays into the model's runtime buffers (weights, activations): the detector keeps the model alive with it
+        self.model = model
+        self.run = model.capture_inference(self.batch, self.size, post=(self.conf_thres, self.iou_thres))
+        self.device = self.run.static_input.device
+        self.nc, self.mk = self.run.post_plan.nc, self.run.post_plan.mk
+        self._plans = OrderedDict()          # (H, W, rates) -> ScenePlan, least recently used first
+        self._plans_max = 4
+        self._side = None
+
+    # ---- buffers
+    def plan(self, H, W):
+        key = (int(H), int(W), self.rates)
+        p = self._plans.pop(key, None)
+        if p is None:
+            while len(self._plans) >= self._plans_max:
+                torch.cuda.synchronize(self.device)                   # launches still reading the evicted buffers finish first
+                self._plans.popitem(last=False)
+            p = ScenePlan(self, int(H), int(W))
+        self._plans[key] = p
+        return p
+
+    # ---- scene placement
+    def _place(self, scene):
+        if isinstance(scene, torch.Tensor):
+            hip.require_device(scene, "TiledDetector")
+            if scene.dtype != torch.uint8 or scene.dim() != 3 or scene.shape[2] != 3 or not scene.is_contiguous():
+                raise RuntimeError("TiledDetector: a device scene must be a contiguous uint8 [H, W, 3] (BGR) tensor")
+            return _Placed(scene, 0, scene.shape[0], scene.shape[1], scene)
+        img = np.asarray(scene)
+        if img.dtype != np.uint8 or img.ndim not in (2, 3):
+            raise RuntimeError("TiledDetector: a host scene must be a uint8 H x W x 3 (BGR) array")
+        pool = A.ImagePool([img], self.device)                           # pinned staging + non-blocking upload (grey -> 3 channels)
+        H, W = pool.shape(0)
+        return _Placed(pool.buf, pool.offset(0), H, W, pool)
+
+    # ---- the device pipeline of one scene
+    def _enqueue(self, placed):
+        H, W = placed.H, placed.W
+        p = self.plan(H, W)
+        st = hip.stream()
+        scene = placed.addr
+        src = []
+        if p.resize_items:
+            A._check_layouts()
+            arr = (A._ResizeItem * len(p.resize_items))()
+            for k, (ri, h, w) in enumerate(p.resize_items):
+                arr[k] = A._ResizeItem(0, p.stage_off[ri], H, W, h, w, A.INTERP_AREA if self.rates[ri] < 1 else A.INTERP_LINEAR, -1)
+            items = A._to_device(arr, self.device)
+            hip.call("ryolo_resize_hsv_batch", scene, hip.ptr(items), len(p.resize_items), max(h * w for _, h, w in p.resize_items), None,
+                     hip.ptr(p.stage), st)
+        for ri, r in enumerate(self.rates):
+            src.append(0 if p.stage_off[ri] is None else p.stage.data_ptr() + p.stage_off[ri] - scene)
+        rows = p.rows.copy()
+        rows[:, 0] = np.asarray(src, dtype=np.int64)[p.rate_of]
+        _h2d(p.win, rows)
+        run, B = self.run, self.batch
+        for g in range(p.groups):
+            w0 = g * B
+            hip.call("ryolo_tile_cut", scene, hip.ptr(p.win), w0, min(B, p.T - w0), self.size, hip.ptr(run.static_input), st)
+            run.graph.replay()
+            p.collect(run.post_plan.out, run.post_plan.num, g)
+        return p.merge(self.merge_iou, self.gt_only)
+
+    # ---- public
+    def run_async(self, scene):
+        """-> (out [max_det, 7] zero padded, num [1] int32), both on the device and owned by the detector (valid until the next scene of the
+        same size).  Nothing is read back."""
+        placed = self._place(scene)
+        out, num = self._enqueue(placed)
+        self._last = placed                  # the scene's memory stays referenced while its launches may be pending
+        return out, num
+
+    def __call__(self, scene):
+        """HxWx3 uint8 BGR numpy array (cv2.imread) or device tensor -> Tensor[n, 7] (x, y, w, h, theta_rad, score, cls) in scene pixels,
+        score descending (ties: window order, then the window's own order)."""
+        out, num = self.run_async(scene)
+        n = int(num.item())                  # the one device -> host read of the scene
+        return out[:n].clone()
+
+    def detect_files(self, paths, imread=None, overlap=True):
+        """Iterate (path, Tensor[n, 7]) over image files.  overlap=True: scene i + 1 is decoded on the host and uploaded on a side stream
+        while scene i runs; the compute stream waits for its upload event (DeviceLoader's pattern)."""
+        from ..datasets.base_dataset import _default_imread
+        imread = imread or _default_imread
+        paths = list(paths)
+        main = torch.cuda.current_stream(self.device)
+        if overlap and self._side is None:
+            self._side = torch.cuda.Stream(device=self.device)
+
+        def load(path):
+            if not overlap:
+                return self._place(imread(path)), None
+            with torch.cuda.stream(self._side):
+                placed = self._place(imread(path))
+                return placed, self._side.record_event()
+
+        nxt = load(paths[0]) if paths else None
+        for i, path in enumerate(paths):
+            placed, ev = nxt
+            if ev is not None:
+                main.wait_event(ev)
+            out, num = self._enqueue(placed)
+            nxt = load(paths[i + 1]) if overlap and i + 1 < len(paths) else None
+            n = int(num.item())
+            res = out[:n].clone()
+            del placed                        # scene i is done: its side-stream memory may be reused
+            if not overlap and i + 1 < len(paths):
+                nxt = load(paths[i + 1])
+            yield path, res
+
+
+# ------------------------------------------------------------------------------------------ DOTA Task1 output
+def write_dota_task1(results, out_dir, class_names):
+    """results {image name: Tensor[n, 7] (x, y, w, h, theta_rad, score, cls) on the device} -> out_dir/Task1_<class>.txt for every class
+    (DOTA's submission format): one line per detection, "name score x1 y1 x2 y2 x3 y3 x4 y4", vertices from xywha2xyxyxyxy on the device;
+    images in the order of `results`, detections in their order.  Returns the list of files written."""
+    import os
+    os.makedirs(out_dir, exist_ok=True)
+    lines = [[] for _ in class_names]
+    for name, dets in results.items():
+        if dets is None or dets.shape[0] == 0:
+            continue
+        d = dets if dets.is_cuda else dets.to(torch.device("cuda", torch.cuda.current_device()))
+        polys = general.xywha2xyxyxyxy(d[:, :5].contiguous()).reshape(-1, 8).cpu().numpy()
+        sc = d[:, 5].cpu().numpy()
+        cl = d[:, 6].cpu().numpy().astype(np.int64)
+        for k in range(len(sc)):
+            if not 0 <= cl[k] < len(class_names):
+                raise ValueError(f"write_dota_task1: class {cl[k]} of {name} has no name")
+            lines[cl[k]].append(f"{name} {sc[k]:.6f} " + " ".join(f"{v:.1f}" for v in polys[k]))
+    files = []
+    for c, cname in enumerate(class_names):
+        path = os.path.join(out_dir, f"Task1_{cname}.txt")
+        with open(path, "w") as f:
+            f.write("".join(line + "\n" for line in lines[c]))
+        files.append(path)
+    return files

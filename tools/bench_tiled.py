@@ -1,0 +1,111 @@
+"""Full-scene (tiled) detection throughput: yolov7 kfiou nc=16 (synth.fill_state weights), a synthetic 4000 x 4000 scene, S=1024,
+overlap=200, batch=8 (25 windows in 4 groups).  Prints one JSON line:
+  scene_ms / windows_per_s        TiledDetector.run_async + the count read, per scene
+  replay_ms                       the same number of bare captured-graph replays (forward + post_process in the graph)
+  glue_ms / glue_share            scene_ms - replay_ms: cut, collect, merge, final order, launches (target <= 5 % of scene time)
+  naive_ms                        the Python loop a user writes today: per-window device slicing + to-tensor, the captured forward without
+                                  post, post_process per group, a host-side shift, per-class nms_rotated
+  files_overlap_ms / files_serial_ms   detect_files over 8 scenes with / without the side-stream upload overlap (decode = an in-memory copy)
+Environment: SCENE (4000), S (1024), OVERLAP (200), B (8), CONF (0.1), N (iterations, 10)."""
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+from ryolov4_amd.lib import general
+from ryolov4_amd.lib.tiled import TiledDetector, tile_plan
+from ryolov4_amd.model.yolo import Yolo
+from ryolov4_amd.synth import CFG, fill_state
+
+dev = torch.device("cuda:0")
+SC, S, OV, B = int(os.environ.get("SCENE", 4000)), int(os.environ.get("S", 1024)), int(os.environ.get("OVERLAP", 200)), int(os.environ.get("B", 8))
+CONF, IOU, N = float(os.environ.get("CONF", 0.1)), 0.4, int(os.environ.get("N", 10))
+
+net = Yolo(16, CFG, "kfiou", "yolov7")
+net.load_state_dict(fill_state(net.state_dict()))
+net.to(dev).eval()
+det = TiledDetector(net, size=S, overlap=OV, batch=B, conf_thres=CONF, iou_thres=IOU)
+scene = np.random.RandomState(0).randint(0, 256, (SC, SC, 3)).astype(np.uint8)
+scene_dev = torch.from_numpy(scene).to(dev)
+wins = tile_plan(SC, SC, S, OV)
+groups = -(-len(wins) // B)
+
+
+def wall(fn, n=N):
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / n
+
+
+def tiled():
+    out, num = det.run_async(scene_dev)
+    return int(num.item())
+
+
+def replays():
+    for _ in range(groups):
+        det.run.graph.replay()
+    torch.cuda.synchronize()
+
+
+bare = net.capture_inference(B, S)                              # forward + decode only: the naive loop runs post_process itself
+
+
+def naive():
+    pad = torch.nn.functional.pad
+    dets = []
+    for g in range(groups):
+        ws = wins[g * B:(g + 1) * B]
+        imgs = torch.zeros((B, 3, S, S), dtype=torch.float32, device=dev)
+        for k, (_, x0, y0) in enumerate(ws):
+            w = scene_dev[y0:y0 + S, x0:x0 + S]
+            w = pad(w.permute(2, 0, 1), (0, S - w.shape[1], 0, S - w.shape[0]), value=114)
+            imgs[k] = w.flip(0).float() / 255
+        _, infer = bare(imgs)
+        res = general.post_process(infer, CONF, IOU)
+        for k, (_, x0, y0) in enumerate(ws):
+            d = res[k].cpu()
+            d[:, 0] += x0
+            d[:, 1] += y0
+            dets.append(d)
+    d = torch.cat(dets).to(dev)
+    keep = []
+    for c in d[:, 6].unique():
+        idx = torch.nonzero(d[:, 6] == c)[:, 0]
+        b = d[idx, :5].clone()
+        b[:, 4] = b[:, 4] / np.pi * 180
+        keep.append(idx[general.nms_rotated(b, d[idx, 5], IOU)])
+    return len(torch.cat(keep)) if keep else 0
+
+
+files = [f"scene{i}" for i in range(8)]
+
+
+def read(path):
+    return scene.copy()                                        # stands in for the decode
+
+
+def run_files(overlap):
+    return sum(len(d) for _, d in det.detect_files(files, imread=read, overlap=overlap))
+
+
+t_scene = wall(tiled)
+t_rep = wall(replays)
+t_naive = wall(naive, max(2, N // 3))
+t_fo = wall(lambda: run_files(True), 2) / len(files)
+t_fs = wall(lambda: run_files(False), 2) / len(files)
+n_tiled, n_naive = tiled(), naive()
+print(json.dumps({"scene": SC, "S": S, "overlap": OV, "batch": B, "windows": len(wins), "groups": groups, "padded_slots": groups * B - len(wins),
+                  "conf_thres": CONF, "detections": n_tiled, "naive_detections": n_naive,
+                  "scene_ms": round(t_scene, 3), "windows_per_s": round(len(wins) / t_scene * 1e3, 1), "replay_ms": round(t_rep, 3),
+                  "glue_ms": round(t_scene - t_rep, 3), "glue_share": round((t_scene - t_rep) / t_scene, 4), "naive_ms": round(t_naive, 3),
+                  "speedup_vs_naive": round(t_naive / t_scene, 2), "files_overlap_ms": round(t_fo, 3), "files_serial_ms": round(t_fs, 3)}))
