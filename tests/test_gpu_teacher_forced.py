@@ -15,7 +15,8 @@ around single launches of its tapes (Graph.probe) every conv + BatchNorm + activ
 against the bf16-storage-emulating torch-CPU oracle (tests/bf16_emu.py), rel-L2 <= 3e-2 per tensor (observed values are written to
 gpurun_out/r03_teacher_forced.json).  The two plan features that move a node's reduction into ANOTHER node's launch (BatchNorm sums in
 the completing data gradient's epilogue, MaxPool gradient in the sibling's store) are switched off here — with them a node's inputs
-are consumed before they can be forced; tests/test_gpu_bnfuse.py and test_gpu_pool.py hold those variants to this one."""
+are consumed before they can be forced.  The first is no longer part of the plans; tests/gemm1x1_cases.py
+(test_maxpool_gradient_in_the_store) holds the second to the plain pool backward."""
 import json
 import os
 
