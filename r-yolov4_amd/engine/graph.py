@@ -112,6 +112,29 @@ def _taps_fwd(k, pad):
     return [(r - pad, s - pad, r * k + s) for r in range(k) for s in range(k)]
 
 
+def _taps_dgrad_s1(k, pad):
+    """Stride-1 data gradient: a correlation of dY with mirrored taps; weight slot r * k + c of the [Cin][tap][Cout] image."""
+    return [(pad - r, pad - c, r * k + c) for r in range(k) for c in range(k)]
+
+
+def _classes_dgrad_s2(k, pad):
+    """Stride-2 data gradient as four output-parity classes [(taps, ph, pw)]: dx[2a + ph][2b + pw] sums only the taps (r, c) whose
+    input row 2 oh - pad + r can be 2a + ph, i.e. (ph + pad - r) even (1 / 2 / 2 / 4 live taps for k = 3, pad = 1), read at
+    dY[a + (ph + pad - r) / 2][b + (pw + pad - c) / 2]."""
+    classes = []
+    for ph in range(2):
+        for pw in range(2):
+            taps = [((ph + pad - r) // 2, (pw + pad - c) // 2, r * k + c) for r in range(k) for c in range(k)
+                    if (ph + pad - r) % 2 == 0 and (pw + pad - c) % 2 == 0]
+            classes.append((taps, ph, pw))
+    return classes
+
+
+def _taps_dgrad_s2d():
+    """Space-to-depth form of the 3x3 stride-2 pad-1 data gradient (weights from ryolo_pack_s2d): 2 x 2 taps over the dY grid."""
+    return [(da, db, 2 * da + db) for da in range(2) for db in range(2)]
+
+
 def _fill_class(tc, taps, oh_add=0, ow_add=0):
     tc.ntaps = len(taps)
     tc.oh_add, tc.ow_add = oh_add, ow_add
@@ -477,7 +500,7 @@ class Graph:
         epi = S.EPI_ACCUM if mode else S.EPI_RAW
         cin = conv.in_channels
         if s == 1:
-            taps = [(pad - r, pad - c, r * k + c) for r in range(k) for c in range(k)]
+            taps = _taps_dgrad_s1(k, pad)
             pl = None
             if pool is not None:
                 assert k == 1 and pool["z"].C == x.C
@@ -486,17 +509,12 @@ class Graph:
         elif (self.rt.s2d_dgrad and k == 3 and pad == 1 and cin <= self.rt.s2d_dgrad_maxc and cin % 8 == 0 and x.H % 2 == 0 and x.W % 2 == 0
               and dy_cin % 32 == 0 and dy_cin == conv.out_channels):
             # narrow stride-2 layer: ONE stride-1 GEMM over the dY grid, N = 4 parities x cin, 2x2 taps, depth-to-space store
-            taps = [(da, db, 2 * da + db) for da in range(2) for db in range(2)]
+            taps = _taps_dgrad_s2d()
             self._gemm(self.bwd, dy, dy_ptr, self.rt.packed_s2d(conv), 4 * cin, 4, dy_cin, x.H // 2, x.W // 2, 1, [(taps, 0, 0)], epi,
                        x.gptr(), x.ld, full=(2, 2, x.H, x.W), s2d=cin)
         else:
             assert s == 2 and x.H % 2 == 0 and x.W % 2 == 0
-            classes = []
-            for ph in range(2):
-                for pw in range(2):
-                    taps = [((ph + pad - r) // 2, (pw + pad - c) // 2, r * k + c) for r in range(k) for c in range(k)
-                            if (ph + pad - r) % 2 == 0 and (pw + pad - c) % 2 == 0]
-                    classes.append((taps, ph, pw))
+            classes = _classes_dgrad_s2(k, pad)
             self._gemm(self.bwd, dy, dy_ptr, pk["wd"], cin, k * k, dy_cin, x.H // 2, x.W // 2, 1, classes, epi, x.gptr(), x.ld,
                        full=(2, 2, x.H, x.W))
 

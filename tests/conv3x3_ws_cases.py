@@ -2,7 +2,7 @@
 none).  Run through tests/test_gpu_conv3x3_ws.py in a child process: the switch is read once per process by the library."""
 import pytest
 
-from tests.test_gpu_conv3x3 import _run
+from tests.test_gpu_conv3x3 import _lattice_epilogues, _run, _run_lattice
 
 pytestmark = pytest.mark.gpu
 
@@ -37,3 +37,17 @@ def test_forced_persistent_kernel_inference_activations(act):
 def test_not_eligible_shapes_stay_on_the_patch_kernel():
     _run(2, 50, 50, 128, 64, expect_kernel=1)           # Cin = 128: the weights do not fit the register file
     _run(2, 20, 30, 64, 64, expect_kernel=1)            # no tile of >= 224 pixels divides 20 x 30
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_forced_persistent_kernel_lattice(shape):
+    """Integer lattices, bit-exact against the float64 reference (tests/conv_gemm_cases.py): every shape, every epilogue."""
+    B, H, W, Cin, Cout = shape
+    _lattice_epilogues(B=B, H=H, W=W, Cin=Cin, Cout=Cout, ld_extra=24, seed=3 + H, expect_kernel=3)
+
+
+def test_forced_persistent_kernel_mirrored_lattice():
+    _run_lattice(2, 50, 50, 64, 64, mirrored=True, expect_kernel=3)
+    _run_lattice(3, 100, 100, 64, 64, mirrored=True, epi=4, ld_extra=8, expect_kernel=3)
+    _run_lattice(2, 50, 50, 128, 64, expect_kernel=1)
+    _run_lattice(2, 20, 30, 64, 64, expect_kernel=1)

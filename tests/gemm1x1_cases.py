@@ -215,3 +215,39 @@ def _run_pool(NB, H, W, Cin, Cout, epi, seed=0):
 @pytest.mark.parametrize("geom", [(2, 20, 20, 128, 256), (3, 10, 14, 256, 128), (1, 6, 6, 64, 136), (2, 50, 50, 128, 256)])
 def test_maxpool_gradient_in_the_store(geom, epi):
     _run_pool(*geom, epi=epi, seed=epi + 2)
+
+
+# ---- the same launches on integer lattices: BIT-EXACT against the float64 reference of tests/conv_ref.py (tests/conv_gemm_cases.py) -----------
+def _run_lattice(M, Cin, Cout, epi, ld_extra=0, seed=0, act=3, kind="round", tally=None):
+    from tests.conv_gemm_cases import fwd
+    return fwd(1, 1, M, Cin, Cout, k=1, epi=epi, act=act, pipe=0x201, kind=kind, ldA_extra=ld_extra + 8, ldC_extra=ld_extra + 8, expect=2, seed=seed,
+               tally=tally, what=f"lattice {M}x{Cin}->{Cout} epi={epi} {kind}")
+
+
+@pytest.mark.parametrize("shape", SHAPES + [(3 * 25 * 25, 128, 200), (9000, 256, 128)])
+def test_shapes_and_epilogues_lattice(shape):
+    """Raw / statistics (accumulated over all tiles of a wave: the whole-column exactness bound covers them) / accumulate bit-identical on both
+    lattices; the activation epilogue within one bf16 ulp + its evaluation bound, >= 99 % bit-identical."""
+    from tests.conv_gemm_cases import Tally
+    for epi, kind in ((0, "round"), (0, "exact"), (1, "exact"), (1, "round"), (4, "round")):
+        _run_lattice(*shape, epi=epi, kind=kind, ld_extra=56 if shape[2] == 200 else 0, seed=epi)
+    t = Tally()
+    for act in (0, 1, 2, 3):
+        _run_lattice(*shape, epi=2, act=act, seed=act, tally=t)
+    t.check("activation epilogue")
+
+
+@pytest.mark.parametrize("epi", [0, 4])
+@pytest.mark.parametrize("geom", [(2, 32, 32, 64), (3, 25, 19, 64), (1, 7, 5, 64), (2, 40, 40, 32), (5, 16, 48, 64), (2, 20, 24, 64)])
+def test_space_to_depth_data_gradient_lattice(geom, epi):
+    from tests.conv_gemm_cases import s2d
+    s2d(*geom, 32, epi=epi, pipe=0x201, expect=2, ldA_extra=32, ldC_extra=32, seed=epi + 1, what=f"lattice s2d {geom} epi={epi}")
+
+
+@pytest.mark.parametrize("epi", [0, 4])
+@pytest.mark.parametrize("geom", [(2, 20, 20, 128, 256), (3, 10, 14, 256, 128), (1, 6, 6, 64, 136), (2, 50, 50, 128, 256)])
+def test_maxpool_gradient_in_the_store_lattice(geom, epi):
+    """On the lattice the fused pool gradient is exact: bf16(bf16(y) + dz where selected), then the accumulate step."""
+    from tests.conv_gemm_cases import fwd
+    NB, H, W, Cin, Cout = geom
+    fwd(NB, H, W, Cin, Cout, k=1, epi=epi, pipe=0x201, pool=True, expect=2, seed=epi + 2, what=f"lattice pool {geom} epi={epi}")

@@ -105,3 +105,37 @@ def test_repeatable_bits_and_ineligible_shapes():
     assert torch.equal(y1, y2) and torch.equal(s1, s2)
     _run(4000, 96, 256, epi=0, expect=0)                # K not a multiple of 64: generic kernel
     _run(4000, 512, 64, epi=0, expect=0)                # fewer than 128 output columns
+
+
+# ---- the same launches on integer lattices: BIT-EXACT against the float64 reference of tests/conv_ref.py (tests/conv_gemm_cases.py) -----------
+def _run_lattice(M, Cin, Cout, epi, ld_extra=0, seed=0, expect=4, act=3, kind="round", tally=None):
+    from tests.conv_gemm_cases import fwd
+    _, _, kv = fwd(1, 1, M, Cin, Cout, k=1, epi=epi, act=act, pipe=0x201, kind=kind, ldA_extra=ld_extra + 8, ldC_extra=ld_extra + 8, expect=expect,
+                   seed=seed, tally=tally, what=f"lattice {M}x{Cin}->{Cout} epi={epi} {kind}")
+    if expect == 4:
+        assert (kv >> 16) & 15 == (4 if Cout <= 128 else 8)
+
+
+def _lattice_epilogues(*shape, **kw):
+    from tests.conv_gemm_cases import Tally
+    for epi, kind in ((0, "round"), (0, "exact"), (1, "exact"), (1, "round"), (4, "round")):
+        _run_lattice(*shape, epi=epi, kind=kind, seed=epi, **kw)
+    t = Tally()
+    for act in (0, 1, 2, 3):
+        _run_lattice(*shape, epi=2, act=act, seed=30 + act, tally=t, **kw)
+    t.check("activation epilogue")
+
+
+@pytest.mark.skipif(not FORCED, reason="run through tests/test_gpu_gemm256.py (RYOLO_GEMM_256=2)")
+@pytest.mark.parametrize("shape", SHAPES + [(17 * 1000, 512, 256)])
+def test_shapes_and_epilogues_lattice(shape):
+    _lattice_epilogues(*shape)
+
+
+@pytest.mark.skipif(not FORCED, reason="run through tests/test_gpu_gemm256.py (RYOLO_GEMM_256=2)")
+def test_channel_slices_and_ineligible_shapes_lattice():
+    _lattice_epilogues(3 * 25 * 25, 128, 200, ld_extra=56)
+    _lattice_epilogues(9000, 512, 128, ld_extra=8)
+    _lattice_epilogues(300, 1024, 128, ld_extra=8)
+    _run_lattice(4000, 96, 256, epi=0, expect=0)
+    _run_lattice(4000, 512, 64, epi=0, expect=0)

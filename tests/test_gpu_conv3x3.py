@@ -149,3 +149,58 @@ def test_persistent_64_channel_kernel_multi_tile(epi):
 def test_persistent_64_channel_kernel_mirrored_taps_and_narrow_output():
     _run(8, 200, 200, 64, 64, mirrored=True, epi=4, seed=20, expect_kernel=3)          # the data-gradient tap order
     _run(8, 200, 200, 64, 40, epi=1, seed=21, expect_kernel=3)                          # Cout = 40: zero weight rows, partial column chunks
+
+
+# ---- the same kernels on integer lattices: BIT-EXACT against the float64 reference of tests/conv_ref.py (tests/conv_gemm_cases.py) ------------
+def _run_lattice(B, H, W, Cin, Cout, epi=0, ld_extra=0, mirrored=False, seed=0, act=3, expect_kernel=1, pipe_extra=0, expect_cols=None, kind="round",
+                 tally=None):
+    """The geometry of _run with lattice operands: raw / statistics / accumulate outputs bit-identical to the reference rounded once, exact
+    statistics on the exact lattice, the activation epilogue within one bf16 ulp + its fp32 evaluation bound (>= 99 % bit-identical)."""
+    from tests.conv_gemm_cases import run_lattice
+    from tests.conv_ref import taps_forward
+    taps = taps_forward(3, 1)
+    if mirrored:
+        taps = [(dh, dw, 8 - wi) for dh, dw, wi in reversed(taps)]
+    _, _, kv = run_lattice(NB=B, IH=H, IW=W, Cin=Cin, Nout=Cout, wtaps=9, OH=H, OW=W, classes=[(taps, 0, 0)], epi=epi, act=act,
+                           pipe=0x1 | 0x200 | 0x400 | pipe_extra, kind=kind, ldA_extra=ld_extra + 8, ldC_extra=ld_extra + 8, expect=expect_kernel,
+                           seed=seed, tally=tally, what=f"lattice {B}x{H}x{W} {Cin}->{Cout} epi={epi} {kind}")
+    if expect_cols is not None:
+        assert ((kv >> 16) & 15) * 32 == expect_cols, f"tile columns {((kv >> 16) & 15) * 32}, expected {expect_cols}"
+
+
+def _lattice_epilogues(tally=None, **kw):
+    """Epilogues 0, 1, 4 on both lattices and epilogue 2 with every activation."""
+    from tests.conv_gemm_cases import Tally
+    t = tally or Tally()
+    for epi, kind in ((0, "round"), (0, "exact"), (1, "exact"), (1, "round"), (4, "round")):
+        _run_lattice(epi=epi, kind=kind, **kw)
+    for act in (0, 1, 2, 3):
+        _run_lattice(epi=2, act=act, tally=t, **kw)
+    if tally is None:
+        t.check("activation epilogue")
+
+
+PATCH_SHAPES = [(2, 50, 50, 64, 128), (3, 25, 25, 96, 128), (1, 20, 30, 32, 64), (2, 13, 13, 64, 192), (1, 100, 100, 32, 64), (2, 7, 9, 160, 72),
+                (3, 25, 25, 64, 64), (2, 25, 25, 64, 128)]
+
+
+@pytest.mark.parametrize("B,H,W,Cin,Cout", PATCH_SHAPES)
+def test_patch_kernel_lattice(B, H, W, Cin, Cout):
+    _lattice_epilogues(B=B, H=H, W=W, Cin=Cin, Cout=Cout, ld_extra=40, seed=H + Cout)
+
+
+@pytest.mark.parametrize("shape", [(2, 50, 50, 64, 128), (2, 13, 13, 64, 192), (3, 25, 25, 96, 136)])
+def test_patch_kernel_64_column_tiles_lattice(shape):
+    B, H, W, Cin, Cout = shape
+    _lattice_epilogues(B=B, H=H, W=W, Cin=Cin, Cout=Cout, seed=60, pipe_extra=0x2000, expect_cols=64)
+
+
+def test_patch_kernel_mirrored_taps_lattice():
+    _lattice_epilogues(B=2, H=50, W=50, Cin=128, Cout=64, mirrored=True, seed=1)
+    _lattice_epilogues(B=2, H=26, W=26, Cin=64, Cout=128, mirrored=True, seed=2)
+
+
+def test_persistent_64_channel_kernel_lattice():
+    _lattice_epilogues(B=8, H=200, W=200, Cin=64, Cout=64, ld_extra=64, seed=10, expect_kernel=3)
+    _lattice_epilogues(B=8, H=200, W=200, Cin=64, Cout=40, seed=21, expect_kernel=3)
+    _run_lattice(8, 200, 200, 64, 64, mirrored=True, epi=4, seed=20, expect_kernel=3)

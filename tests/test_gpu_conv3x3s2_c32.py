@@ -191,3 +191,35 @@ def test_streaming_stride2_dgrad(B, H, W):       # (the odd map: the last input 
 def test_streaming_stride2_dgrad_slices():
     _run_dgrad(2, 64, 64, ldy_extra=64, ldx_extra=32, seed=11)
     _run_dgrad(1, 66, 130, ldy_extra=8, ldx_extra=24, seed=12)
+
+
+# ---- the same launches on integer lattices: BIT-EXACT against the float64 reference of tests/conv_ref.py (tests/conv_gemm_cases.py) -----------
+def _run_lattice(B, H, W, Cout, epi=0, ldx_extra=0, ldc_extra=0, act=3, seed=0, expect=5, kind="round", tally=None):
+    from tests.conv_gemm_cases import fwd
+    fwd(B, H, W, 32, Cout, s=2, epi=epi, act=act, pipe=0x701, kind=kind, ldA_extra=ldx_extra + 8, ldC_extra=ldc_extra + 8, expect=expect, seed=seed,
+        tally=tally, what=f"lattice {B}x{H}x{W} 32->{Cout} epi={epi} {kind}")
+
+
+def _run_dgrad_lattice(B, H, W, ldy_extra=0, ldx_extra=0, seed=0, expect=6, kind="round"):
+    from tests.conv_gemm_cases import s2d
+    s2d(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64, 32, H=H, W=W, epi=0, pipe=0x701, kind=kind, ldA_extra=ldy_extra + 8, ldC_extra=ldx_extra + 8,
+        expect=expect, seed=seed, what=f"lattice dgrad {B}x{H}x{W} {kind}")
+
+
+@pytest.mark.parametrize("B,H,W,Cout", [(2, 64, 64, 64), (1, 96, 200, 64), (3, 65, 47, 64), (1, 34, 70, 64), (5, 16, 16, 64), (1, 400, 400, 64),
+                                        (2, 64, 64, 48), (2, 50, 70, 8), (1, 66, 130, 64), (2, 48, 80, 64)])
+def test_streaming_stride2_forward_lattice(B, H, W, Cout):
+    """Every shape of this file; the epilogues this kernel has (raw, statistics, folded BatchNorm + every activation)."""
+    from tests.conv_gemm_cases import Tally
+    for epi, kind in ((0, "round"), (0, "exact"), (1, "exact"), (1, "round")):
+        _run_lattice(B, H, W, Cout, epi=epi, kind=kind, ldx_extra=32, ldc_extra=24, seed=B + H + epi)
+    t = Tally()
+    for act in (0, 1, 2, 3):
+        _run_lattice(B, H, W, Cout, epi=2, act=act, seed=7 + act, tally=t)
+    t.check("activation epilogue")
+
+
+@pytest.mark.parametrize("B,H,W", [(2, 64, 64), (1, 96, 200), (3, 66, 46), (1, 34, 70), (5, 16, 16), (1, 400, 400), (3, 65, 47), (1, 66, 130)])
+def test_streaming_stride2_dgrad_lattice(B, H, W):
+    for kind in ("round", "exact"):
+        _run_dgrad_lattice(B, H, W, ldy_extra=64, ldx_extra=24, seed=B + H, kind=kind)

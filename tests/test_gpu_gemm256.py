@@ -20,6 +20,16 @@ def test_default_dispatch_takes_the_long_k_layers(epi):
     _run(64 * 25 * 25, 2048, 512, epi=epi, seed=6 + epi, expect=0)         # 314 tiles: stays on the generic kernel
 
 
+@pytest.mark.parametrize("epi,kind", [(0, "round"), (1, "exact"), (1, "round"), (2, "round"), (4, "round")])
+def test_default_dispatch_lattice(epi, kind):
+    """The same four layers on integer lattices, bit-exact against the float64 reference (tests/conv_gemm_cases.py)."""
+    from tests.gemm256_cases import _run_lattice
+    _run_lattice(64 * 50 * 50, 512, 512, epi=epi, kind=kind, ld_extra=64 if epi else 0, seed=epi)
+    _run_lattice(64 * 50 * 50, 1024, 128, epi=epi, kind=kind, seed=3 + epi, expect=0)
+    _run_lattice(64 * 50 * 50, 1024, 256, epi=epi, kind=kind, seed=9 + epi)
+    _run_lattice(64 * 25 * 25, 2048, 512, epi=epi, kind=kind, seed=6 + epi, expect=0)
+
+
 def _child(files, timeout):
     import gc
     import torch
