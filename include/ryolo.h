@@ -137,8 +137,9 @@ int ryolo_conv_gemm_stats_rows(int64_t M, int Nout, int pipe, int* rows);
 /* which kernel ryolo_conv_gemm runs for *p and the number of partial-statistics rows its epilogue 1 writes; `kernel` may be null.
  * *kernel & 0xff: 0 generic implicit GEMM, 1 the 3x3 stride-1 halo-patch kernel (pipe bit 0x200, eligible layers), 2 the weight-stationary
  * persistent 1x1 kernel (RYOLO_GEMM_WS and its tapped / pool-gradient instantiations), 3 the persistent weight-stationary 3x3 kernel for 64 -> <= 64
- * channels (conv3x3_ws.hip), 4 the 256-wide 8-wave pointwise kernel (gemm256.hip; bits 16-19 = tile columns / 32); for 0 also bit 0x100 = the 1x1
- * instantiation, bits 12-15 = tile rows / 64, bits 16-19 = tile columns / 32 */
+ * channels (conv3x3_ws.hip), 4 the 256-wide 8-wave pointwise kernel (gemm256.hip), 5 the streaming 3x3 stride-2 forward for 32 input channels
+ * (conv3x3s2_c32.hip), 6 that layer's space-to-depth data gradient; for 0, 1 and 4 bits 16-19 = tile columns / 32; for 0 also bit 0x100 = the 1x1
+ * instantiation and bits 12-15 = tile rows / 64.  stats_rows: pixel tiles (0, 1, 4), waves (2), workgroups (3, 5, 6) */
 int ryolo_conv_gemm_plan(const ConvGemmParams* p, int* stats_rows, int* kernel);
 /* weight gradient: split-K over output pixels into p->partial ([splitk][Cout][taps*Cin] fp32, size from _plan), then a
  * deterministic reduction that accumulates into the torch-layout .grad [Cout][Cin][kh*kw] (no float atomics). */
@@ -146,8 +147,8 @@ int ryolo_conv_wgrad_plan(const WgradParams* p, int* splitk, size_t* workspace_b
 int ryolo_conv_wgrad(const WgradParams* p, ryolo_stream_t stream);
 /* which kernel ryolo_conv_wgrad launches for *p: 0 generic split-K (register-staged, or the LDS-DMA pointwise form), 1 the 3x3 stride-1 halo-ring
  * kernel (needs p->zeros), 2 the tapped LDS-DMA kernel (tapped / strided layers with > 64 output channels; needs p->zeros), 3 the 8-wave
- * 256 x 256-tile pointwise kernel (stride-1 1x1 layers with Cin >= 256 and Cout > 128; needs p->zeros), 4 the 8-wave parity-plane ring kernel
- * (3x3 stride-2 pad-1 layers with more than 64 output channels; needs p->zeros) */
+ * 256 x 256-tile pointwise kernel (stride-1 1x1 layers with Cin >= 256 and Cout > 128; needs p->zeros).  (4, the parity-plane ring kernel for 3x3
+ * stride-2 layers, was retired in round 6 and is no longer returned.)  Answers RY_OK with kernel 0 also for blocks ryolo_conv_wgrad rejects. */
 int ryolo_conv_wgrad_kernel(const WgradParams* p, int* kernel);
 /* launch shape of that kernel: workgroups, waves per workgroup (8: a workgroup holds its CU exclusively and the grid is sized to part of the chip) */
 int ryolo_conv_wgrad_grid(const WgradParams* p, int* workgroups, int* waves);

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define RY_OK 0
 #define RY_ERR_ARG 1
@@ -16,6 +17,11 @@
     } while (0)
 
 static inline int64_t ry_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Environment knobs (docs/KNOBS.md): atoi of the variable, `d` when it is unset; every site keeps the value in a function-local
+// `static const`, so a knob is read once per process.
+static inline int ry_knob_int(const char* name, int d) { const char* e = getenv(name); return e ? atoi(e) : d; }
+static inline bool ry_knob_set(const char* name) { return getenv(name) != nullptr; }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE function attribute: one flag word per (kernel, device), set with a relaxed
 // atomic so that two host threads racing through the first launch both end up with the attribute in place (the call is idempotent).

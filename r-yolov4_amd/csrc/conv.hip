@@ -25,8 +25,6 @@
 #include <type_traits>
 #include <stdlib.h>
 
-template <int N> __device__ __forceinline__ void gemm_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
 
 #define BK 32
@@ -189,7 +187,6 @@ __global__ __launch_bounds__(256, NST >= 5 ? 1 : 2) void conv_gemm_kernel(const 
             __syncthreads();
         }
 
-
     } else if constexpr (PIPE == 1) {
         // ---- LDS-DMA ring: NSTG stages of (BM + BN) x KB bf16, filled by global_load_lds_dwordx4 (no VGPR staging) ----
         // One wave instruction moves 1 KiB = RPP rows x (2*KB) bytes into a lane-linear LDS image, so the bank swizzle of the
@@ -325,11 +322,11 @@ __global__ __launch_bounds__(256, NST >= 5 ? 1 : 2) void conv_gemm_kernel(const 
         const int extra = __builtin_amdgcn_readfirstlane((wave < PCS_A % 4 ? 1 : 0) + (wave < PCS_B % 4 ? 1 : 0));
         auto wait_inflight = [&](auto stages) {                               // allow `stages` later stages to stay in flight
             constexpr int S = decltype(stages)::value;
-            if constexpr (XTR == 0) { gemm_wait_vm<S * LPS>(); }
+            if constexpr (XTR == 0) { wait_vm<S * LPS>(); }
             else {
-                if (extra == XTR) gemm_wait_vm<S * LPS>();
-                else if (XTR == 2 && extra == 1) gemm_wait_vm<S * (LPS_LO + 1)>();
-                else gemm_wait_vm<S * LPS_LO>();
+                if (extra == XTR) wait_vm<S * LPS>();
+                else if (XTR == 2 && extra == 1) wait_vm<S * (LPS_LO + 1)>();
+                else wait_vm<S * LPS_LO>();
             }
         };
 #pragma unroll
@@ -784,7 +781,7 @@ __global__ __launch_bounds__(256, NST >= 5 ? 1 : 2) void conv_gemm_kernel(const 
 // pixel-major LDS rows of 128 channels + 32 pad: row stride 320 B = 64 B (mod 256 B), so the 4 rows x 32 B a 16-lane group of
 // ds_read_b64_tr_b16 touches (and the neighbouring group's +32 B) fall on 8 disjoint bank ranges -> conflict free
 #define WG_LD 160
-// exact n / d for 0 <= n < 2^31 as mulhi(n, m) >> s (host: wg_magic): output pixels per image and per row — the X gather decomposes
+// exact n / d for 0 <= n < 2^31 as mulhi(n, m) >> s (host: ry_magic_div): output pixels per image and per row — the X gather decomposes
 // its pixel index without the loop-carried (image, row, column) walk of the first version, whose `while` carries compiled to a chain of
 // divergent branches (5 per K step; ~270 instructions per K step for 8 MFMAs).
 struct WgMagic { unsigned m_img, s_img, m_row, s_row; };
@@ -1118,8 +1115,8 @@ __global__ __launch_bounds__(256, PX == 64 ? 2 : 3) void wgrad1x1_dma_kernel(con
             for (int e = 0; e < 16; e++) acc[i][j][e] = 0.f;
 
     for (int s = 0; s < nk; s++) {
-        if (NS == 2 || s + 1 >= nk) gemm_wait_vm<0>();             // NS == 3: the stage issued during step s - 1 (operands of step s + 1) may stay in flight
-        else gemm_wait_vm<NP>();
+        if (NS == 2 || s + 1 >= nk) wait_vm<0>();             // NS == 3: the stage issued during step s - 1 (operands of step s + 1) may stay in flight
+        else wait_vm<NP>();
         __builtin_amdgcn_s_barrier();                               // stage s visible to every wave; stage s - 1 fully consumed
         if (s + NS - 1 < nk) issue_stage();
 #pragma unroll
@@ -1269,8 +1266,8 @@ __global__ __launch_bounds__(256, 3) void wgrad_taps_dma_kernel(const WgradParam
             for (int e = 0; e < 16; e++) acc[i][j][e] = 0.f;
 
     for (int s = 0; s < nk; s++) {
-        if (s + 1 >= nk) gemm_wait_vm<0>();                          // the stage requested during step s - 1 (operands of step s + 1) may stay in flight
-        else gemm_wait_vm<NP>();
+        if (s + 1 >= nk) wait_vm<0>();                          // the stage requested during step s - 1 (operands of step s + 1) may stay in flight
+        else wait_vm<NP>();
         __builtin_amdgcn_s_barrier();
         if (s + NS - 1 < nk) issue_stage();
         const unsigned base = lds_addr(wt_lds + (s % NS) * STB);
@@ -1388,13 +1385,14 @@ static bool gemm_ident(const ConvGemmParams& p)
 // single tap (0, 0) on the identity grid, input grid == output grid: the 1x1 instantiations (no tile decomposition, no tap table)
 static bool gemm_is_t1(const ConvGemmParams& p)
 {
-    static const bool t1_on = !(getenv("RYOLO_GEMM_T1") && atoi(getenv("RYOLO_GEMM_T1")) == 0);      // A/B knob
+    static const bool t1_on = ry_knob_int("RYOLO_GEMM_T1", 1) != 0;      // A/B knob
     return (p.pipe & 0xff) == 1 && gemm_ident(p) && t1_on && p.cls[0].ntaps == 1 && p.cls[0].dh[0] == 0 && p.cls[0].dw[0] == 0 && p.cls[0].widx[0] == 0 &&
            p.sh == 1 && p.sw == 1 && p.IH == p.OH && p.IW == p.OW;
 }
 
+// t1: the route's 1x1 bit (gemm_is_t1; LDS-DMA mainloop only)
 template <int BM, int BN, int WM, int WN, int PIPE, int KB = 32>
-static int launch_gemm(const ConvGemmParams& p, hipStream_t stream)
+static int launch_gemm(const ConvGemmParams& p, bool t1, hipStream_t stream)
 {
     const int64_t M = (int64_t)p.NB * p.OH * p.OW;
     const int64_t gm = ry_cdiv(M, BM), gn = ry_cdiv(p.Nout, BN);
@@ -1402,13 +1400,12 @@ static int launch_gemm(const ConvGemmParams& p, hipStream_t stream)
     dim3 grid((unsigned)(gm * gn), 1, p.nclasses);
     ConvGemmParams q = p;
     // several tap classes over one input: class-chunked 1-D order (conv_gemm_kernel); RYOLO_GEMM_CLS_CHUNK = tiles per chunk (0: classes on blockIdx.z)
-    static const int cls_chunk = getenv("RYOLO_GEMM_CLS_CHUNK") ? atoi(getenv("RYOLO_GEMM_CLS_CHUNK")) : 1024;     // same-box img/s: 0 -> 934.0, 256 -> 936.3, 512 -> 936.0, 1024 -> 937.9 (three alternating runs each)
+    static const int cls_chunk = ry_knob_int("RYOLO_GEMM_CLS_CHUNK", 1024);     // same-box img/s: 0 -> 934.0, 256 -> 936.3, 512 -> 936.0, 1024 -> 937.9 (three alternating runs each)
     if (p.nclasses > 1 && cls_chunk >= 16 && gm * gn * p.nclasses <= 0x7fffffff) {
         q.pipe = (p.pipe & 0xffff) | ((cls_chunk / 16 > 0xfff ? 0xfff : cls_chunk / 16) << 16);
         grid = dim3((unsigned)(gm * gn * p.nclasses), 1, 1);
     }
     const bool ident = gemm_ident(p);
-    const bool t1 = PIPE == 1 && gemm_is_t1(p);
     if constexpr (PIPE == 1) {
         if (t1) {
             if (p.epi == EPI_ACCUM) hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, PIPE, KB, 1, true, true>), grid, dim3(256), 0, stream, q);
@@ -1428,11 +1425,11 @@ static int launch_gemm(const ConvGemmParams& p, hipStream_t stream)
 
 // deep-ring instantiations of the 128 x 128 tile for grids that leave a workgroup alone (or in a pair) on its CU
 template <int NST>
-static int launch_gemm_deep(const ConvGemmParams& p, hipStream_t stream)
+static int launch_gemm_deep(const ConvGemmParams& p, bool t1, hipStream_t stream)
 {
     const int64_t M = (int64_t)p.NB * p.OH * p.OW;
     const dim3 grid((unsigned)(ry_cdiv(M, 128) * ry_cdiv(p.Nout, 128)), 1, 1);
-    const bool t1 = gemm_is_t1(p), acc = p.epi == EPI_ACCUM;
+    const bool acc = p.epi == EPI_ACCUM;
     if (t1 && acc) hipLaunchKernelGGL((conv_gemm_kernel<128, 128, 2, 2, 1, 32, 1, true, true, NST>), grid, dim3(256), 0, stream, p);
     else if (t1) hipLaunchKernelGGL((conv_gemm_kernel<128, 128, 2, 2, 1, 32, 0, true, true, NST>), grid, dim3(256), 0, stream, p);
     else if (acc) hipLaunchKernelGGL((conv_gemm_kernel<128, 128, 2, 2, 1, 32, 1, true, false, NST>), grid, dim3(256), 0, stream, p);
@@ -1441,7 +1438,7 @@ static int launch_gemm_deep(const ConvGemmParams& p, hipStream_t stream)
 }
 static int gemm_deep_stages(const ConvGemmParams& p)
 {
-    static const int mode = getenv("RYOLO_GEMM_DEEP") ? atoi(getenv("RYOLO_GEMM_DEEP")) : 1;     // 0 off; 1 by grid size; 4 / 6 force that depth on every eligible launch (tests)
+    static const int mode = ry_knob_int("RYOLO_GEMM_DEEP", 1);     // 0 off; 1 by grid size; 4 / 6 force that depth on every eligible launch (tests)
     if (!mode || (p.pipe & 0xff) != 1 || !gemm_ident(p) || p.Nout <= 64 || (p.pipe & 0x800)) return 0;
     if (mode == 4 || mode == 6) return mode;
     const int64_t tiles = ry_cdiv((int64_t)p.NB * p.OH * p.OW, 128) * ry_cdiv(p.Nout, 128);
@@ -1450,18 +1447,20 @@ static int gemm_deep_stages(const ConvGemmParams& p)
     return tiles <= 256 ? 6 : (tiles <= 512 ? 4 : 0);
 }
 
-// rows of one generic-kernel tile for these parameters: the SAME decision ryolo_conv_gemm's dispatch makes (statistics rows = M tiles)
+// 64-channel (full 128-byte line) stages: measured +1..5 % on 3x3 layers up to 256 channels, -4..-10 % on 1x1 / 512-channel
+// layers (tools/bench_conv.py matrix in DESIGN.md); 0x100 forces 32-channel stages for A/B runs
 static bool gemm_k64(const ConvGemmParams& p) { return (p.Cin % 64 == 0) && p.cls[0].ntaps > 1 && p.Cin <= 256 && !(p.pipe & 0x100); }
+// <= 64 output columns: 256 x 64 tiles (each wave 64 x 64: 8 MFMAs per K step; the 128 x 64 tile gives a wave 64 x 32 = 4 MFMAs per
+// step around the same barrier / DMA issue) when the grid still fills the chip; RYOLO_GEMM_N64 = 0 restores 128 x 64 (A/B)
 static bool gemm_wide_n64(const ConvGemmParams& p)
 {
-    static const int n64_wide = getenv("RYOLO_GEMM_N64") ? atoi(getenv("RYOLO_GEMM_N64")) : 1;   // 0 off, 1 large grids, 2 every grid (parity tests on small grids)
+    static const int n64_wide = ry_knob_int("RYOLO_GEMM_N64", 1);   // 0 off, 1 large grids, 2 every grid (parity tests on small grids)
     return (p.pipe & 0xff) && p.Nout > 32 && p.Nout <= 64 && n64_wide && !gemm_k64(p) && ((int64_t)p.NB * p.OH * p.OW >= 256ll * 1536 || n64_wide == 2);
 }
-static int gemm_tile_rows(const ConvGemmParams& p) { return (p.Nout <= 32 || gemm_wide_n64(p)) ? 256 : 128; }
 
 extern "C" int ryolo_conv_gemm_stats_rows(int64_t M, int Nout, int pipe, int* rows)
 {
-    // upper bound of the [2][Nout] partial-statistics rows the EPI_STATS epilogue writes (exact: ryolo_conv_gemm_plan, which knows the tile)
+    // upper bound of the [2][Nout] partial-statistics rows the EPI_STATS epilogue writes (exact: ryolo_conv_gemm_plan, which knows the route)
     if (!rows) return RY_ERR_ARG;
     (void)pipe;
     *rows = (int)ry_cdiv(M, Nout <= 32 ? 256 : 128);               // (n tiles share the row; every generic tile is 128 pixels but the 256-pixel ones)
@@ -1515,65 +1514,98 @@ static int gemm_check(const ConvGemmParams& p)
     return RY_OK;
 }
 
+// ---- the forward / data-gradient route ----------------------------------------------------------------------------------------------
+// THE decision which kernel family (and which generic tile) a parameter block runs on.  ryolo_conv_gemm_plan reports it, ryolo_conv_gemm
+// launches it; a new family is one arm here and one `case` in ryolo_conv_gemm.  family = *kernel & 0xff of ryolo_conv_gemm_plan (ryolo.h).
+enum { GEMM_GENERIC = 0, GEMM_PATCH3 = 1, GEMM_WS1 = 2, GEMM_WS3 = 3, GEMM_G256 = 4, GEMM_S2C = 5, GEMM_S2C_DGRAD = 6 };
+struct GemmRoute {
+    int family;
+    int stats_rows;                       // [2][Nout] partial-statistics rows the EPI_STATS epilogue of that kernel writes
+    int tile_rows, tile_cols;             // generic kernel: 256 | 128 x 32 | 64 | 128; patch / gemm256 kernels: tile_cols = their BN, tile_rows = 0
+    int kb, deep;                         // generic kernel: channels per stage (32 | 64), ring depth of the deep 128 x 128 instantiations (0 | 4 | 6)
+    bool dma, t1, head;                   // generic kernel: LDS-DMA mainloop (pipe & 0xff), the 1x1 instantiation, the fused detection-head epilogue
+    S2cGeom s2c;                          // the geometry of the chosen family, filled once
+    Ws3Geom ws3;
+    P3Geom p3;
+    G256Geom g256;
+    Ws1Geom ws1;
+};
+
+// RY_OK, or the status ryolo_conv_gemm_plan returns for a block no kernel takes.  Order: the fused head first (one tap on the identity grid, so neither
+// 3x3 kernel could claim it, and both stride-2 geometries reject head_attrs), then the most specific family that accepts the block.
+static int gemm_route(const ConvGemmParams& p, GemmRoute& r)
+{
+    r = GemmRoute{};
+    if (p.Cin <= 0 || p.Cin % BK || p.Nout <= 0 || p.nclasses < 1 || p.nclasses > 4) return RY_ERR_ARG;
+    const int64_t M = (int64_t)p.NB * p.OH * p.OW;
+    r.kb = 32;
+    if (p.head_attrs) {                                       // detection head in its final layout: the 128 x 128 1x1 instantiation or nothing
+        if (p.head_attrs < 7 || p.Nout % p.head_attrs || p.epi != EPI_F32_BIAS) return RY_ERR_ARG;
+        if (!gemm_is_t1(p) || M > 0x7fffffff) return RY_ERR_UNSUPPORTED;
+        r.family = GEMM_GENERIC;
+        r.head = r.t1 = r.dma = true;
+        r.tile_rows = r.tile_cols = 128;
+        r.stats_rows = (int)ry_cdiv(M, 128);
+        return RY_OK;
+    }
+    if (s2c_geometry(p, r.s2c)) {                             // streaming 3x3 stride-2 forward, 32 input channels (conv3x3s2_c32.hip): one row per workgroup
+        r.family = GEMM_S2C;
+        r.stats_rows = r.s2c.nwg;
+        return RY_OK;
+    }
+    if (s2c_dgrad_geometry(p, r.s2c)) {                       // ... and its data gradient in the space-to-depth form (no statistics epilogue)
+        r.family = GEMM_S2C_DGRAD;
+        r.stats_rows = r.s2c.nwg;
+        return RY_OK;
+    }
+    if ((p.pipe & 0x200) && ws3_geometry(p, r.ws3)) {         // persistent weight-stationary 3x3 (conv3x3_ws.hip): one statistics row per workgroup
+        r.family = GEMM_WS3;
+        r.stats_rows = r.ws3.nwg;
+        return RY_OK;
+    }
+    if ((p.pipe & 0x200) && p3_geometry(p, r.p3)) {           // halo-patch 3x3 (conv3x3.hip; r06: 64-column tiles also for wide layers on small grids)
+        r.family = GEMM_PATCH3;
+        r.tile_cols = r.p3.BN;
+        r.stats_rows = (int)r.p3.gm;
+        return RY_OK;
+    }
+    if (g256_geometry(p, r.g256)) {                           // 256-wide tiles for long-K pointwise layers (gemm256.hip): one statistics row per pixel tile
+        r.family = GEMM_G256;
+        r.tile_cols = r.g256.BN;
+        r.stats_rows = (int)r.g256.gm;
+        return RY_OK;
+    }
+    if (ws1_geometry(p, r.ws1)) {                             // weight-stationary persistent 1x1 (gemm1x1.hip): one row per wave
+        r.family = GEMM_WS1;
+        r.stats_rows = r.ws1.stats_rows;
+        return RY_OK;
+    }
+    r.family = GEMM_GENERIC;
+    r.dma = (p.pipe & 0xff) != 0;
+    r.t1 = gemm_is_t1(p);
+    if (p.Nout <= 32) { r.tile_rows = 256; r.tile_cols = 32; }
+    else if (gemm_wide_n64(p)) { r.tile_rows = 256; r.tile_cols = 64; }
+    else if ((r.deep = r.dma ? gemm_deep_stages(p) : 0)) { r.tile_rows = 128; r.tile_cols = 128; }
+    else {
+        r.tile_rows = 128;
+        r.tile_cols = (p.Nout <= 64 || (r.dma && (p.pipe & 0x800))) ? 64 : 128;      // 0x800: A/B, 64-wide N tiles everywhere
+        if (r.dma && gemm_k64(p)) r.kb = 64;
+    }
+    r.stats_rows = (int)ry_cdiv(M, r.tile_rows);              // statistics rows = M tiles
+    return RY_OK;
+}
+
 // Which kernel ryolo_conv_gemm will run for these parameters and how many [2][Nout] partial-statistics rows its EPI_STATS
-// epilogue writes (= number of M tiles).  kernel: 0 generic implicit GEMM (conv.hip), 1 3x3 halo-patch kernel (conv3x3.hip,
-// selected by pipe bit 0x200 when the layer is eligible), 2 weight-stationary persistent 1x1 kernel (gemm1x1.hip; rows = waves),
-// 3 persistent weight-stationary 3x3 kernel for 64 -> <= 64 channels (conv3x3_ws.hip; rows = workgroups), 4 the 256-wide pointwise GEMM for long
-// reductions (gemm256.hip; bits 16-19 = tile columns / 32), 5 the streaming 3x3 stride-2 forward for 32 input channels (conv3x3s2_c32.hip;
-// rows = workgroups), 6 the same layer's space-to-depth data gradient.
+// epilogue writes.  *kernel: the family in bits 0-7 (ryolo.h); generic kernel: bit 8 = the 1x1 instantiation (T1), bits 12-15 = tile rows / 64;
+// generic, patch and gemm256 kernels: bits 16-19 = tile columns / 32 (what rocprofv3 lists as separate kernels; tools and bench.py label their
+// per-kernel tables with it)
 extern "C" int ryolo_conv_gemm_plan(const ConvGemmParams* pp, int* stats_rows, int* kernel)
 {
     if (!pp || !stats_rows) return RY_ERR_ARG;
-    const ConvGemmParams& p = *pp;
-    if (p.Cin <= 0 || p.Cin % BK || p.Nout <= 0 || p.nclasses < 1 || p.nclasses > 4) return RY_ERR_ARG;
-    if (p.head_attrs) {                                       // detection head in its final layout: the 128 x 128 1x1 instantiation or nothing
-        if (p.head_attrs < 7 || p.Nout % p.head_attrs || p.epi != EPI_F32_BIAS) return RY_ERR_ARG;
-        if (!gemm_is_t1(p) || (int64_t)p.NB * p.OH * p.OW > 0x7fffffff) return RY_ERR_UNSUPPORTED;
-        *stats_rows = (int)ry_cdiv((int64_t)p.NB * p.OH * p.OW, 128);
-        if (kernel) *kernel = 0 | 0x100 | (2 << 12) | (4 << 16);
-        return RY_OK;
-    }
-    S2cGeom sg;
-    if (s2c_geometry(p, sg)) {                                     // streaming 3x3 stride-2 forward, 32 input channels (conv3x3s2_c32.hip): one row per workgroup
-        *stats_rows = sg.nwg;
-        if (kernel) *kernel = 5;
-        return RY_OK;
-    }
-    if (s2c_dgrad_geometry(p, sg)) {                               // ... and its data gradient in the space-to-depth form (no statistics epilogue)
-        *stats_rows = sg.nwg;
-        if (kernel) *kernel = 6;
-        return RY_OK;
-    }
-    Ws3Geom w3;
-    if ((p.pipe & 0x200) && ws3_geometry(p, w3)) {                 // persistent weight-stationary 3x3 (conv3x3_ws.hip): one statistics row per workgroup
-        *stats_rows = w3.nwg;
-        if (kernel) *kernel = 3;
-        return RY_OK;
-    }
-    P3Geom g;
-    if ((p.pipe & 0x200) && p3_geometry(p, g)) {
-        *stats_rows = (int)g.gm;
-        if (kernel) *kernel = 1 | ((g.BN / 32) << 16);            // bits 16-19 = tile columns / 32 (r06: 64-column tiles also for wide layers on small grids)
-        return RY_OK;
-    }
-    G256Geom g2;
-    if (g256_geometry(p, g2)) {                                     // 256-wide tiles for long-K pointwise layers (gemm256.hip): one statistics row per pixel tile
-        *stats_rows = (int)g2.gm;
-        if (kernel) *kernel = 4 | ((g2.BN / 32) << 16);
-        return RY_OK;
-    }
-    Ws1Geom wg;
-    if (p.nclasses == 1 && ws1_geometry(p, wg)) {
-        *stats_rows = wg.stats_rows;
-        if (kernel) *kernel = 2;
-        return RY_OK;
-    }
-    // generic kernel: bits 8 = the 1x1 instantiation (T1), bits 12-15 = tile rows / 64, bits 16-19 = tile columns / 32 (what rocprofv3 lists
-    // as separate kernels; tools and bench.py label their per-kernel tables with it)
-    const int rows = gemm_tile_rows(p);
-    const int cols = p.Nout <= 32 ? 32 : ((p.Nout <= 64 || ((p.pipe & 0xff) && (p.pipe & 0x800))) ? 64 : 128);
-    if (kernel) *kernel = 0 | (gemm_is_t1(p) ? 0x100 : 0) | ((rows / 64) << 12) | ((cols / 32) << 16);
-    *stats_rows = (int)ry_cdiv((int64_t)p.NB * p.OH * p.OW, rows);
+    GemmRoute r;
+    if (const int rc = gemm_route(*pp, r)) return rc;
+    *stats_rows = r.stats_rows;
+    if (kernel) *kernel = r.family | (r.family == GEMM_GENERIC && r.t1 ? 0x100 : 0) | ((r.tile_rows / 64) << 12) | ((r.tile_cols / 32) << 16);
     return RY_OK;
 }
 
@@ -1587,47 +1619,36 @@ extern "C" int ryolo_conv_gemm(const ConvGemmParams* pp, hipStream_t stream)
         if (p.cls[c].ntaps < 1 || p.cls[c].ntaps > RY_MAX_TAPS) return RY_ERR_ARG;
     if (p.epi == EPI_STATS && (!p.stats || p.nclasses != 1)) return RY_ERR_ARG;
     if ((int64_t)p.NB * p.OH * p.OW <= 0) return RY_OK;
-    {
-        S2cGeom sg;
-        if (s2c_geometry(p, sg)) return s2c_launch(p, sg, stream);
-        if (s2c_dgrad_geometry(p, sg)) return s2c_dgrad_launch(p, sg, stream);
+    if ((p.pipe & 0xff) && !p.zeros) return RY_ERR_ARG;       // the LDS-DMA mainloops read padding from the zero page (every specialised family checks it too)
+    GemmRoute r;
+    if (const int rc = gemm_route(p, r)) return rc;
+    switch (r.family) {
+    case GEMM_S2C: return s2c_launch(p, r.s2c, stream);
+    case GEMM_S2C_DGRAD: return s2c_dgrad_launch(p, r.s2c, stream);
+    case GEMM_WS3: return ws3_launch(p, r.ws3, stream);
+    case GEMM_PATCH3: return p3_launch(p, r.p3, stream);
+    case GEMM_G256: return g256_launch(p, r.g256, stream);
+    case GEMM_WS1: return ws1_launch(p, r.ws1, stream);
     }
-    if (p.pipe & 0x200) {
-        Ws3Geom w3;
-        if (ws3_geometry(p, w3)) return ws3_launch(p, w3, stream);
-        P3Geom g;
-        if (p3_geometry(p, g)) return p3_launch(p, g, stream);
-    }
-    if (p.head_attrs) {                                       // detection head in its final layout: the 1x1 instantiation of the generic kernel only
-        if (!p.zeros) return RY_ERR_ARG;
-        const int64_t M = (int64_t)p.NB * p.OH * p.OW;
-        const int64_t gm = ry_cdiv(M, 128), gn = ry_cdiv(p.Nout, 128);
-        if (gm * gn > 0x7fffffff || M > 0x7fffffff) return RY_ERR_UNSUPPORTED;
+    if (r.head) {                                             // detection head in its final layout: the 1x1 instantiation of the generic kernel only
+        const int64_t gm = ry_cdiv((int64_t)p.NB * p.OH * p.OW, 128), gn = ry_cdiv(p.Nout, 128);
+        if (gm * gn > 0x7fffffff) return RY_ERR_UNSUPPORTED;
         hipLaunchKernelGGL((conv_gemm_kernel<128, 128, 2, 2, 1, 32, 3, true, true>), dim3((unsigned)(gm * gn)), dim3(256), 0, stream, p);
         return hipGetLastError() == hipSuccess ? RY_OK : RY_ERR_LAUNCH;
     }
-    if (p.pipe & 0xff) {
-        if (!p.zeros) return RY_ERR_ARG;
-        G256Geom g2;
-        if (g256_geometry(p, g2)) return g256_launch(p, g2, stream);
-        Ws1Geom wg;
-        if (ws1_geometry(p, wg)) return ws1_launch(p, wg, stream);
-        // 64-channel (full 128-byte line) stages: measured +1..5 % on 3x3 layers up to 256 channels, -4..-10 % on 1x1 / 512-channel
-        // layers (tools/bench_conv.py matrix in DESIGN.md); 0x100 forces 32-channel stages for A/B runs
-        const bool k64 = gemm_k64(p);
-        if (p.Nout <= 32) return launch_gemm<256, 32, 4, 1, 1>(p, stream);
-        // <= 64 output columns: 256 x 64 tiles (each wave 64 x 64: 8 MFMAs per K step; the 128 x 64 tile gives a wave 64 x 32 = 4 MFMAs per
-        // step around the same barrier / DMA issue) when the grid still fills the chip; RYOLO_GEMM_N64 = 0 restores 128 x 64 (A/B)
-        if (gemm_wide_n64(p)) return launch_gemm<256, 64, 4, 1, 1>(p, stream);
-        if (const int deep = gemm_deep_stages(p)) return deep == 6 ? launch_gemm_deep<6>(p, stream) : launch_gemm_deep<4>(p, stream);
-        if (p.Nout <= 64 || (p.pipe & 0x800)) return k64 ? launch_gemm<128, 64, 2, 2, 1, 64>(p, stream) : launch_gemm<128, 64, 2, 2, 1>(p, stream);   // 0x800: A/B, 64-wide N tiles everywhere
-        return k64 ? launch_gemm<128, 128, 2, 2, 1, 64>(p, stream) : launch_gemm<128, 128, 2, 2, 1>(p, stream);
+    if (r.deep) return r.deep == 6 ? launch_gemm_deep<6>(p, r.t1, stream) : launch_gemm_deep<4>(p, r.t1, stream);
+    if (!r.dma) {
+        if (r.tile_cols == 32) return launch_gemm<256, 32, 4, 1, 0>(p, false, stream);
+        if (r.tile_cols == 64) return launch_gemm<128, 64, 2, 2, 0>(p, false, stream);
+        return launch_gemm<128, 128, 2, 2, 0>(p, false, stream);
     }
-    if (p.Nout <= 32) return launch_gemm<256, 32, 4, 1, 0>(p, stream);
-    if (p.Nout <= 64) return launch_gemm<128, 64, 2, 2, 0>(p, stream);
-    return launch_gemm<128, 128, 2, 2, 0>(p, stream);
+    if (r.tile_rows == 256)
+        return r.tile_cols == 32 ? launch_gemm<256, 32, 4, 1, 1>(p, r.t1, stream) : launch_gemm<256, 64, 4, 1, 1>(p, r.t1, stream);
+    if (r.tile_cols == 64) return r.kb == 64 ? launch_gemm<128, 64, 2, 2, 1, 64>(p, r.t1, stream) : launch_gemm<128, 64, 2, 2, 1>(p, r.t1, stream);
+    return r.kb == 64 ? launch_gemm<128, 128, 2, 2, 1, 64>(p, r.t1, stream) : launch_gemm<128, 128, 2, 2, 1>(p, r.t1, stream);
 }
 
+// ---- the weight-gradient route ---------------------------------------------------------------------------------------------------------
 static int wgrad_geometry(WgradParams& p, int& bm, int& gx, int& gy)
 {
     if (p.Cin <= 0 || p.Cin % BK || p.ldX % 8 || p.ldY % 8 || p.Cout <= 0 || p.CoutPad % 8 || p.CoutPad < p.Cout || p.CoutPad > p.ldY ||
@@ -1640,7 +1661,7 @@ static int wgrad_geometry(WgradParams& p, int& bm, int& gx, int& gy)
     gy = (int)ry_cdiv((int64_t)p.ntaps * (p.Cin / BK), cpt);
     // 512 = 2 workgroups x 256 CUs (r04: +0.4 % step over 768, a third fewer split-K slabs; 384 equal, 256 -0.8 %; r01-r03 measured 768 best of
     // 768 / 1024 / 1536 / 2560 against the BatchNorm kernels of those rounds); env knob for A/B runs
-    static const int target = getenv("RYOLO_WGRAD_BLOCKS") ? atoi(getenv("RYOLO_WGRAD_BLOCKS")) : 512;
+    static const int target = ry_knob_int("RYOLO_WGRAD_BLOCKS", 512);
     int64_t want = ry_cdiv(target, (int64_t)gx * gy);                // one full wave of resident workgroups by default
     int64_t maxsplit = ry_cdiv(M, 16 * BK);                          // at least 16 K-steps per split
     int64_t sk = want > maxsplit ? maxsplit : want;
@@ -1651,55 +1672,85 @@ static int wgrad_geometry(WgradParams& p, int& bm, int& gx, int& gy)
     return RY_OK;
 }
 
+// RYOLO_WGRAD_P1 (A/B knob): bit 0 pointwise addressing, bit 1 the LDS-DMA kernel, bit 2 its 64-pixel steps (on since the end of r04: with two
+// workgroups per CU on the side stream — wgrad_geometry — the two-stage 64-pixel form is +0.45 % on the step, three alternating runs; at three
+// per CU, r03, it was neutral)
+static int wgrad_p1_mode() { static const int v = ry_knob_int("RYOLO_WGRAD_P1", 7); return v; }
+static bool wgrad_pointwise(const WgradParams& p)
+{
+    return p.ntaps == 1 && p.dh[0] == 0 && p.dw[0] == 0 && p.sh == 1 && p.sw == 1 && p.IH == p.OH && p.IW == p.OW && p.OH * p.OW > 1 && (wgrad_p1_mode() & 1);
+}
+static bool wgrad_dma_ok(const WgradParams& p) { return p.zeros && ((reinterpret_cast<uintptr_t>(p.dY) | reinterpret_cast<uintptr_t>(p.X)) & 15) == 0; }
+// tapped / strided layers with more than 64 output channels: the LDS-DMA ring with the gather on the request side (RYOLO_WGRAD_TAPS_DMA=0: A/B)
+static bool wgrad_taps_dma(const WgradParams& p, int bm)
+{
+    static const int on = ry_knob_int("RYOLO_WGRAD_TAPS_DMA", 1);
+    return on && !wgrad_pointwise(p) && bm == 128 && wgrad_dma_ok(p) && (int64_t)p.NB * p.OH * p.OW < (1ll << 31);
+}
+
+// THE decision which split-K kernel a weight gradient runs on, with its split and launch shape: ryolo_conv_wgrad_plan / _kernel / _grid report
+// it, ryolo_conv_wgrad launches it; a new family is one arm here and one `case` there.  kernel = what ryolo_conv_wgrad_kernel reports (ryolo.h).
+enum { WGRAD_GENERIC = 0, WGRAD_RING3 = 1, WGRAD_TAPS_DMA = 2, WGRAD_1X1_8W = 3 };
+enum { WGV_REG, WGV_REG_P1, WGV_DMA32, WGV_DMA64 };          // instantiations of WGRAD_GENERIC: conv_wgrad_kernel<bm, p1>, wgrad1x1_dma_kernel<32 | 64>
+struct WgradRoute {
+    int kernel, variant, bm;
+    int splitk, slabs;                    // K ranges; fp32 slabs the workspace holds and launch_wgrad_reduce sums (= what the plan reports as splitk)
+    int64_t kchunk;
+    int workgroups, waves;
+    W3Geom g3;
+    W1x8Geom g8;
+};
+
+// Fills p.splitk / p.kchunk (the generic kernels read them from the block) and r.  Returns the status of the block's argument check; r.kernel is
+// filled even then (ryolo_conv_wgrad_kernel answers for blocks the launch rejects: the two specialised geometries check all they read themselves).
+static int wgrad_route(WgradParams& p, WgradRoute& r)
+{
+    r = WgradRoute{};
+    int gx = 0, gy = 0;
+    const int rc = wgrad_geometry(p, r.bm, gx, gy);
+    if (w3_geometry(p, r.g3)) {                               // 3x3 stride-1 layers: halo-ring kernels (conv3x3.hip, conv3x3_wgrad8.hip)
+        r.kernel = WGRAD_RING3;
+        r.splitk = r.g3.splitk; r.slabs = r.g3.slabs; r.kchunk = r.g3.kchunk;
+        r.workgroups = r.g3.gx * r.g3.gc * r.g3.splitk;
+        r.waves = r.g3.v8 ? 8 : 4;
+    } else if (w1x8_geometry(p, r.g8)) {                      // wide pointwise layers: 8-wave 256 x 256 tiles (wgrad1x1_8w.hip)
+        r.kernel = WGRAD_1X1_8W;
+        r.splitk = r.slabs = r.g8.splitk; r.kchunk = r.g8.kchunk;
+        r.workgroups = r.g8.gx * r.g8.gy * r.g8.splitk;
+        r.waves = 8;
+    } else if (rc == RY_OK) {
+        const bool p1 = wgrad_pointwise(p);
+        // pointwise layers wider than 64 output channels: the LDS-DMA ring kernel (same tiles, same slabs: bm == 128 gives gx = ceil(Cout / 128),
+        // gy = ceil(Cin / 128) there too)
+        if (p1 && r.bm == 128 && (wgrad_p1_mode() & 2) && wgrad_dma_ok(p)) r.variant = (wgrad_p1_mode() & 4) ? WGV_DMA64 : WGV_DMA32;
+        else if (wgrad_taps_dma(p, r.bm)) r.kernel = WGRAD_TAPS_DMA;
+        else r.variant = p1 ? WGV_REG_P1 : WGV_REG;
+        r.splitk = r.slabs = p.splitk; r.kchunk = p.kchunk;
+        r.workgroups = (int)((int64_t)gx * gy * p.splitk);
+        r.waves = 4;
+    }
+    return rc;
+}
+
 extern "C" int ryolo_conv_wgrad_plan(const WgradParams* pp, int* splitk, size_t* workspace_bytes)
 {
     if (!pp || !splitk || !workspace_bytes) return RY_ERR_ARG;
     WgradParams p = *pp;
-    int bm, gx, gy;
-    const int rc = wgrad_geometry(p, bm, gx, gy);
-    if (rc) return rc;
-    W3Geom g3;
-    if (w3_geometry(p, g3)) p.splitk = g3.slabs;               // 3x3 stride-1 layers: halo-ring kernel (conv3x3.hip)
-    else {
-        int sk8, gx8, gy8;
-        int64_t kc8;
-        if (w1x8_geometry(p, &sk8, &kc8, &gx8, &gy8)) p.splitk = sk8;      // wide pointwise layers: 8-wave 256 x 256 tiles (wgrad1x1_8w.hip)
-    }
-    *splitk = p.splitk;
-    *workspace_bytes = (size_t)p.splitk * p.Cout * p.ntaps * p.Cin * sizeof(float);
+    WgradRoute r;
+    if (const int rc = wgrad_route(p, r)) return rc;
+    *splitk = r.slabs;
+    *workspace_bytes = (size_t)r.slabs * p.Cout * p.ntaps * p.Cin * sizeof(float);
     return RY_OK;
 }
 
-static bool wgrad_pointwise(const WgradParams& p)
-{
-    return p.ntaps == 1 && p.dh[0] == 0 && p.dw[0] == 0 && p.sh == 1 && p.sw == 1 && p.IH == p.OH && p.IW == p.OW && p.OH * p.OW > 1 &&
-           !(getenv("RYOLO_WGRAD_P1") && (atoi(getenv("RYOLO_WGRAD_P1")) & 1) == 0);
-}
-// tapped / strided layers with more than 64 output channels: the LDS-DMA ring with the gather on the request side (RYOLO_WGRAD_TAPS_DMA=0: A/B)
-static bool wgrad_taps_dma(const WgradParams& p, int bm)
-{
-    static const int on = getenv("RYOLO_WGRAD_TAPS_DMA") ? atoi(getenv("RYOLO_WGRAD_TAPS_DMA")) : 1;
-    return on && !wgrad_pointwise(p) && bm == 128 && p.zeros && ((reinterpret_cast<uintptr_t>(p.dY) | reinterpret_cast<uintptr_t>(p.X)) & 15) == 0 &&
-           (int64_t)p.NB * p.OH * p.OW < (1ll << 31);
-}
-
-// 0: generic split-K kernels (conv.hip: register-staged, or the LDS-DMA pointwise form), 1: 3x3 stride-1 halo-ring kernel (conv3x3.hip),
-// 2: tapped LDS-DMA kernel (conv.hip), 3: the 8-wave 256 x 256 pointwise kernel (wgrad1x1_8w.hip) — what ryolo_conv_wgrad will launch
-// (4 was the parity-plane ring kernel for 3x3 stride-2 layers, r05: parity-green, step-neutral, retired in r06 — git history keeps it)
+// what ryolo_conv_wgrad will launch (codes: ryolo.h); RY_OK with kernel 0 also for blocks ryolo_conv_wgrad rejects
 extern "C" int ryolo_conv_wgrad_kernel(const WgradParams* pp, int* kernel)
 {
     if (!pp || !kernel) return RY_ERR_ARG;
-    W3Geom g3;
-    *kernel = 0;
-    if (w3_geometry(*pp, g3)) { *kernel = 1; return RY_OK; }
     WgradParams p = *pp;
-    {
-        int sk8, gx8, gy8;
-        int64_t kc8;
-        if (w1x8_geometry(p, &sk8, &kc8, &gx8, &gy8)) { *kernel = 3; return RY_OK; }
-    }
-    int bm, gx, gy;
-    if (wgrad_geometry(p, bm, gx, gy) == RY_OK && wgrad_taps_dma(p, bm)) *kernel = 2;
+    WgradRoute r;
+    wgrad_route(p, r);
+    *kernel = r.kernel;
     return RY_OK;
 }
 
@@ -1710,24 +1761,10 @@ extern "C" int ryolo_conv_wgrad_grid(const WgradParams* pp, int* workgroups, int
 {
     if (!pp || !workgroups || !waves) return RY_ERR_ARG;
     WgradParams p = *pp;
-    int bm, gx, gy;
-    const int rc = wgrad_geometry(p, bm, gx, gy);
-    if (rc) return rc;
-    W3Geom g3;
-    if (w3_geometry(p, g3)) {
-        *workgroups = g3.gx * g3.gc * g3.splitk;
-        *waves = g3.v8 ? 8 : 4;
-        return RY_OK;
-    }
-    int sk8, gx8, gy8;
-    int64_t kc8;
-    if (w1x8_geometry(p, &sk8, &kc8, &gx8, &gy8)) {
-        *workgroups = gx8 * gy8 * sk8;
-        *waves = 8;
-        return RY_OK;
-    }
-    *workgroups = gx * gy * p.splitk;
-    *waves = 4;
+    WgradRoute r;
+    if (const int rc = wgrad_route(p, r)) return rc;
+    *workgroups = r.workgroups;
+    *waves = r.waves;
     return RY_OK;
 }
 
@@ -1736,68 +1773,32 @@ extern "C" int ryolo_conv_wgrad(const WgradParams* pp, hipStream_t stream)
     if (!pp) return RY_ERR_ARG;
     WgradParams p = *pp;
     if (!p.dY || !p.X || !p.dW || !p.partial) return RY_ERR_ARG;
-    int bm, gx, gy;
-    const int rc = wgrad_geometry(p, bm, gx, gy);
-    if (rc) return rc;
+    WgradRoute r;
+    if (const int rc = wgrad_route(p, r)) return rc;
     if ((int64_t)p.NB * p.OH * p.OW <= 0) return RY_OK;
-    W3Geom g3;
-    if (w3_geometry(p, g3)) {
-        const int rc3 = w3_launch(p, g3, stream);
-        if (rc3) return rc3;
-        launch_wgrad_reduce(p, g3.slabs, stream);
-        RY_CHECK_LAUNCH();
-        return RY_OK;
-    }
-    {
-        int sk8, gx8, gy8;
-        int64_t kc8;
-        if (w1x8_geometry(p, &sk8, &kc8, &gx8, &gy8)) {
-            const int rc8 = w1x8_launch(p, stream);
-            if (rc8) return rc8;
-            launch_wgrad_reduce(p, sk8, stream);
-            RY_CHECK_LAUNCH();
-            return RY_OK;
-        }
-    }
-    if ((int64_t)p.NB * p.OH * p.OW >= (1ll << 31)) return RY_ERR_UNSUPPORTED;       // 32-bit pixel indices in the gather
-    auto wg_magic = [](unsigned d, unsigned& m, unsigned& sh) {      // n / d == mulhi(n, m) >> sh for 0 <= n < 2^31
-        if (d < 2) { m = 0; sh = 0; return; }                        // division by one: flagged with m == 0
-        unsigned l = 0;
-        while ((1ull << l) < d) l++;
-        m = (unsigned)((((unsigned long long)1 << (31 + l)) + d - 1) / d);
-        sh = l - 1;
-    };
-    WgMagic mg;
-    wg_magic((unsigned)(p.OH * p.OW), mg.m_img, mg.s_img);
-    wg_magic((unsigned)p.OW, mg.m_row, mg.s_row);
-    const bool p1 = wgrad_pointwise(p);
-    const dim3 wgrid((unsigned)((int64_t)gx * gy * p.splitk));
-    // pointwise layers wider than 64 output channels: the LDS-DMA ring kernel (same tiles, same slabs: bm == 128 gives gx = ceil(Cout / 128),
-    // gy = ceil(Cin / 128) there too); 0x2 in RYOLO_WGRAD_P1 switches it off for A/B runs
-    // bit 0 pointwise addressing, bit 1 the LDS-DMA kernel, bit 2 its 64-pixel steps (on since the end of r04: with two workgroups per CU on the side
-    // stream — wgrad_geometry — the two-stage 64-pixel form is +0.45 % on the step, three alternating runs; at three per CU, r03, it was neutral)
-    static const int p1_mode = getenv("RYOLO_WGRAD_P1") ? atoi(getenv("RYOLO_WGRAD_P1")) : 7;
-    if (p1 && bm == 128 && (p1_mode & 2) && p.zeros && ((reinterpret_cast<uintptr_t>(p.dY) | reinterpret_cast<uintptr_t>(p.X)) & 15) == 0) {
-        if (p1_mode & 4) hipLaunchKernelGGL(wgrad1x1_dma_kernel<64>, wgrid, dim3(256), 0, stream, p);      // 0x4: 64-pixel K steps (A/B)
-        else hipLaunchKernelGGL(wgrad1x1_dma_kernel<32>, wgrid, dim3(256), 0, stream, p);
-        launch_wgrad_reduce(p, p.splitk, stream);
-        RY_CHECK_LAUNCH();
-        return RY_OK;
-    }
-    if (wgrad_taps_dma(p, bm)) {
-        hipLaunchKernelGGL(wgrad_taps_dma_kernel, wgrid, dim3(256), 0, stream, p, mg);
-        launch_wgrad_reduce(p, p.splitk, stream);
-        RY_CHECK_LAUNCH();
-        return RY_OK;
-    }
-    if (bm == 64) {
-        if (p1) hipLaunchKernelGGL((conv_wgrad_kernel<64, true>), wgrid, dim3(256), 0, stream, p, mg);
-        else hipLaunchKernelGGL((conv_wgrad_kernel<64, false>), wgrid, dim3(256), 0, stream, p, mg);
-    } else {
-        if (p1) hipLaunchKernelGGL((conv_wgrad_kernel<128, true>), wgrid, dim3(256), 0, stream, p, mg);
+    switch (r.kernel) {
+    case WGRAD_RING3:
+        if (const int rc = w3_launch(p, r.g3, stream)) return rc;
+        break;
+    case WGRAD_1X1_8W:
+        if (const int rc = w1x8_launch(p, r.g8, stream)) return rc;
+        break;
+    default: {
+        if ((int64_t)p.NB * p.OH * p.OW >= (1ll << 31)) return RY_ERR_UNSUPPORTED;       // 32-bit pixel indices in the gather
+        WgMagic mg;
+        ry_magic_div((unsigned)(p.OH * p.OW), mg.m_img, mg.s_img);
+        ry_magic_div((unsigned)p.OW, mg.m_row, mg.s_row);
+        const dim3 wgrid((unsigned)r.workgroups);
+        if (r.kernel == WGRAD_TAPS_DMA) hipLaunchKernelGGL(wgrad_taps_dma_kernel, wgrid, dim3(256), 0, stream, p, mg);
+        else if (r.variant == WGV_DMA64) hipLaunchKernelGGL(wgrad1x1_dma_kernel<64>, wgrid, dim3(256), 0, stream, p);
+        else if (r.variant == WGV_DMA32) hipLaunchKernelGGL(wgrad1x1_dma_kernel<32>, wgrid, dim3(256), 0, stream, p);
+        else if (r.bm == 64 && r.variant == WGV_REG_P1) hipLaunchKernelGGL((conv_wgrad_kernel<64, true>), wgrid, dim3(256), 0, stream, p, mg);
+        else if (r.bm == 64) hipLaunchKernelGGL((conv_wgrad_kernel<64, false>), wgrid, dim3(256), 0, stream, p, mg);
+        else if (r.variant == WGV_REG_P1) hipLaunchKernelGGL((conv_wgrad_kernel<128, true>), wgrid, dim3(256), 0, stream, p, mg);
         else hipLaunchKernelGGL((conv_wgrad_kernel<128, false>), wgrid, dim3(256), 0, stream, p, mg);
     }
-    launch_wgrad_reduce(p, p.splitk, stream);
+    }
+    launch_wgrad_reduce(p, r.slabs, stream);
     RY_CHECK_LAUNCH();
     return RY_OK;
 }

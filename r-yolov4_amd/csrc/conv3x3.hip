@@ -28,22 +28,6 @@
 
 extern __shared__ __attribute__((aligned(1024))) unsigned char p3_lds[];
 
-template <int K> __device__ __forceinline__ void wait_vm()
-{
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K) : "memory");
-}
-
-template <int U, int N> struct P3Unroll {
-    template <class F> static __device__ __forceinline__ void run(F& f)
-    {
-        f(std::integral_constant<int, U>{});
-        P3Unroll<U + 1, N>::run(f);
-    }
-};
-template <int N> struct P3Unroll<N, N> {
-    template <class F> static __device__ __forceinline__ void run(F&) {}
-};
-
 // EPI is a template parameter: with the epilogue selected by run-time branches the one kernel body carried every variant (17 k instructions
 // behind the loop) and the training epilogues ran 10-13 k cycles per workgroup.  (r02-r05 also carried a `BS` parameter: BatchNorm-backward sums
 // folded into the store loop — slower than the stand-alone reduce pass at every size since r04, retired in r06.)
@@ -313,7 +297,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_patch_kernel(const ConvGemmPar
             __builtin_amdgcn_sched_barrier(0);
             s++;
         };
-        P3Unroll<0, 9>::run(step);
+        ry_unroll<0, 9>::run(step);
     }
 #ifdef P3_TIMING
     const unsigned long long T2 = __builtin_readcyclecounter();
@@ -558,7 +542,7 @@ static bool p3_geometry_bn(const ConvGemmParams& p, P3Geom& g, int bn_force)
     // tiles (p3_geometry below: 26.6 / 56.6 / 39.3 / 18.6 / 60.7 us for the 25^2 256, 25^2 512, 50^2 256, 50^2 128, 32^2 512 cases); batch 1:
     // 25^2 256 -> 256 45.2 -> 27.4 us, 50^2 128 -> 128 27.2 -> 19.1, 25^2 512 -> 512 81.4 -> 46.6.  RYOLO_P3_MIN_WGS: A/B knob (512 ~ the r05
     // rule).  0x400 forces the kernel (tests).
-    static const int min_wgs = getenv("RYOLO_P3_MIN_WGS") ? atoi(getenv("RYOLO_P3_MIN_WGS")) : 4;
+    static const int min_wgs = ry_knob_int("RYOLO_P3_MIN_WGS", 4);
     if (g.gm * ry_cdiv(p.Nout, 64) < min_wgs && !(p.pipe & 0x400)) { g.mode = 0; return false; }      // (counted in 64-column tiles: what a small grid runs)
     return true;
 }
@@ -567,7 +551,7 @@ bool p3_geometry(const ConvGemmParams& p, P3Geom& g)
 {
     if (!p3_geometry_bn(p, g, 0)) return false;
     // fewer 128-column workgroups than CUs: 64-column tiles double the grid (RYOLO_P3_SMALL_BN64 = the grid size below which it applies; 0: off)
-    static const int small64 = getenv("RYOLO_P3_SMALL_BN64") ? atoi(getenv("RYOLO_P3_SMALL_BN64")) : 256;
+    static const int small64 = ry_knob_int("RYOLO_P3_SMALL_BN64", 256);
     // (0x400 = the tests' "force this kernel" bit keeps the 128-column tile; 0x2000 forces the 64-column one)
     if (g.BN == 128 && ((g.gm * g.gn < small64 && !(p.pipe & 0x400)) || (p.pipe & 0x2000))) {
         P3Geom g64;
@@ -580,7 +564,7 @@ template <int BN, int WM, int WN, int EPI> static int p3_launch_t(const ConvGemm
 {
     static RyLdsAttr attr;
     if (ry_max_dynamic_lds(attr, reinterpret_cast<const void*>(&conv3x3_patch_kernel<BN, WM, WN, EPI>), 160 * 1024)) return RY_ERR_LAUNCH;
-    static const unsigned ldspad = getenv("RYOLO_P3_LDSPAD") ? (unsigned)atoi(getenv("RYOLO_P3_LDSPAD")) : 0u;   // occupancy experiments
+    static const unsigned ldspad = (unsigned)ry_knob_int("RYOLO_P3_LDSPAD", 0);   // occupancy experiments
     hipLaunchKernelGGL((conv3x3_patch_kernel<BN, WM, WN, EPI>), dim3((unsigned)(g.gm * g.gn)), dim3(256), g.lds_bytes + ldspad, stream, p, g);
     return hipGetLastError() == hipSuccess ? RY_OK : RY_ERR_LAUNCH;
 }
@@ -1024,7 +1008,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad64_kernel(const WgradPara
                 bh[I] = lds_tr16(xr_a + ((lane_b + sb + 256u) & bmask));
             }
         };
-        P3Unroll<0, PF>::run(read_b);
+        ry_unroll<0, PF>::run(read_b);
         bf16x8 af[2 * NH];
         auto mma = [&](auto ic) {
             constexpr int I = decltype(ic)::value;
@@ -1082,7 +1066,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad64_kernel(const WgradPara
                 else prep_dy();
             }
         };
-        P3Unroll<0, NF>::run(mma);
+        ry_unroll<0, NF>::run(mma);
         __builtin_amdgcn_sched_barrier(0);
     }
 #ifdef W3_TIMING
@@ -1125,19 +1109,13 @@ bool w3_geometry(const WgradParams& p, W3Geom& g)
     if (g.Mp >= (1ll << 31)) return false;                        // 32-bit stream coordinates
     for (int t = 0; t < 9; t++) g.toff[t] = p.dh[t] * g.PWp + p.dw[t];
     for (int t = 0; t < 9; t++) g.tap_of[(p.dh[t] + 1) * 3 + p.dw[t] + 1] = t;
-    auto magic = [](unsigned d, unsigned& m, unsigned& sh) {         // n / d == mulhi(n, m) >> sh for 0 <= n < 2^31 (d >= 3 here: padded sizes)
-        unsigned l = 0;
-        while ((1ull << l) < d) l++;
-        m = (unsigned)((((unsigned long long)1 << (31 + l)) + d - 1) / d);
-        sh = l - 1;
-    };
-    magic((unsigned)(g.HPp * g.PWp), g.m_img, g.s_img);
-    magic((unsigned)g.PWp, g.m_row, g.s_row);
+    ry_magic_div((unsigned)(g.HPp * g.PWp), g.m_img, g.s_img);     // (d >= 3 here: padded sizes)
+    ry_magic_div((unsigned)g.PWp, g.m_row, g.s_row);
     // round 5: the 8-wave form (conv3x3_wgrad8.hip: 2 x (5 | 4) accumulator blocks per wave, rings of any length) where it applies
     if (w8_geometry(p, g)) { g.ok = 1; return true; }
     g.co64 = p.Cout <= 64 ? 1 : 0;
     // RYOLO_W3_STEP64 (A/B knob): bit 0 = 64-pixel K steps for <= 64 output channels, bit 1 = for the 128-channel tiles (conv3x3_wgrad64_kernel)
-    static const int step64 = getenv("RYOLO_W3_STEP64") ? atoi(getenv("RYOLO_W3_STEP64")) : 3;
+    static const int step64 = ry_knob_int("RYOLO_W3_STEP64", 3);
     bool s64 = (step64 >> (g.co64 ? 0 : 1)) & 1;
     int need = 2 * (g.PWp + 1) + (s64 ? 209 : 160);
     int rx = 256;
@@ -1156,20 +1134,18 @@ bool w3_geometry(const WgradParams& p, W3Geom& g)
     // one workgroup per CU (r04; 512 = two per CU until then): with the BatchNorm passes at 5-8 waves per SIMD on the main stream the side stream
     // does better with fewer, longer workgroups (half the split-K slabs, prologue amortised over twice the steps): same-box step 863 -> 874 img/s
     // at 256, 868 at 128 / 192, 860 at 768 (A/B knob)
-    static const int w3_target = getenv("RYOLO_W3_BLOCKS") ? atoi(getenv("RYOLO_W3_BLOCKS")) : 256;
+    static const int w3_target = ry_knob_int("RYOLO_W3_BLOCKS", 256);
     int64_t sk = ry_cdiv(w3_target, (int64_t)g.gx * g.gc);
-    static const int minsteps = getenv("RYOLO_W3_MINSTEPS") ? atoi(getenv("RYOLO_W3_MINSTEPS")) : 24;   // measured 24 / 48 / 128: shorter splits fill the chip, the two-halo prologue still amortises
-    const int64_t maxsplit = g.Mp / ((int64_t)minsteps * 32);      // K-steps per split: the ring prologue (2 halos) must amortise
+    const int64_t maxsplit = g.Mp / ((int64_t)w3_minsteps() * 32);      // K-steps per split: the ring prologue (2 halos) must amortise
     if (sk > maxsplit) sk = maxsplit;
     // small problems stay on the generic kernel, whose finer tiles fill the chip better (measured: 16 x 100^2 x 32 -> 64: 0.6x here)
-    static const bool force = getenv("RYOLO_W3_FORCE") != nullptr;   // A/B runs: ignore the size heuristic
     if (sk < 1) sk = 1;
-    if ((int64_t)g.gx * g.gc * sk < 128 && !force) return false;
+    if ((int64_t)g.gx * g.gc * sk < 128 && !w3_force()) return false;
     const int kstep = g.step64 ? 64 : 32;
     g.kchunk = ry_cdiv(ry_cdiv(g.Mp, sk), kstep) * kstep;
     g.splitk = (int)ry_cdiv(g.Mp, g.kchunk);
     g.lds_bytes = (g.step64 ? 2u * (g.co64 ? 8192u : 16384u) : W3_NS * (g.co64 ? 4096u : 8192u)) + (unsigned)g.RX * 64u;
-    static const int w3_mirror = getenv("RYOLO_W3_MIRROR") ? atoi(getenv("RYOLO_W3_MIRROR")) : 1;      // A/B knob
+    static const int w3_mirror = ry_knob_int("RYOLO_W3_MIRROR", 1);      // A/B knob
     g.mirror = (g.step64 && w3_mirror && g.lds_bytes + 1024u <= 80u * 1024u) ? 1 : 0;
     if (g.mirror) g.lds_bytes += 1024u;
     g.slabs = g.splitk * (g.co64 ? 2 : 1);

@@ -32,19 +32,6 @@ extern __shared__ __attribute__((aligned(1024))) unsigned char w8_lds[];
 
 #define W8_MIRROR 32                                               // ring rows repeated behind the ring (lane row <= 11, +2 taps, +4 second read)
 
-template <int K> __device__ __forceinline__ void w8_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K) : "memory"); }
-
-template <int U, int N> struct W8Unroll {
-    template <class F> static __device__ __forceinline__ void run(F& f)
-    {
-        f(std::integral_constant<int, U>{});
-        W8Unroll<U + 1, N>::run(f);
-    }
-};
-template <int N> struct W8Unroll<N, N> {
-    template <class F> static __device__ __forceinline__ void run(F&) {}
-};
-
 // waits tied to fragment halves (conv_internal.h: the consumer cannot move above the wait, the halves are joined behind it)
 template <int N> __device__ __forceinline__ void w8_wait6(ry_s16x4& a, ry_s16x4& b, ry_s16x4& c, ry_s16x4& d, ry_s16x4& e, ry_s16x4& f)
 {
@@ -158,11 +145,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad8_kernel(const WgradParam
     prep_x();                                                         // the requests of step 0 (operands of step PD)
     prep_dy();
     auto wait_pending = [&]() {                                       // "at most `pend` of my requests in flight": in-order return = everything older has landed
-        if (pend == 0) w8_wait_vm<0>();
-        else if (pend == 1) w8_wait_vm<1>();
-        else if (pend == 2) w8_wait_vm<2>();
-        else if (pend == 3) w8_wait_vm<3>();
-        else w8_wait_vm<4>();
+        if (pend == 0) wait_vm<0>();
+        else if (pend == 1) wait_vm<1>();
+        else if (pend == 2) wait_vm<2>();
+        else if (pend == 3) wait_vm<3>();
+        else wait_vm<4>();
     };
 
     // ---- fragment addressing: transposed reads, lane -> (pixel row, channel) inside a 16-lane group (conv.hip)
@@ -229,7 +216,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad8_kernel(const WgradParam
                 bl[U] = lds_tr16_off<dwi * 64>(gaddr[gi]);
                 bh[U] = lds_tr16_off<dwi * 64 + 256>(gaddr[gi]);
             };
-            W8Unroll<0, PF>::run(read_u);
+            ry_unroll<0, PF>::run(read_u);
             bf16x8 af[2][2];
             auto unit = [&](auto uc) {
                 constexpr int U = decltype(uc)::value;
@@ -267,7 +254,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad8_kernel(const WgradParam
                     else prep_dy();
                 }
             };
-            W8Unroll<0, NU>::run(unit);
+            ry_unroll<0, NU>::run(unit);
             __builtin_amdgcn_sched_barrier(0);
             rp += 64;
             if (rp >= RX) rp -= RX;
@@ -308,10 +295,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wgrad8_kernel(const WgradParam
 // grid, split, LDS.  false: stay on the 4-wave kernels.
 bool w8_geometry(const WgradParams& p, W3Geom& g)
 {
-    static const int on = getenv("RYOLO_W3_V8") ? atoi(getenv("RYOLO_W3_V8")) : 1;          // A/B knob: 0 = the 4-wave kernels of r03 / r04
+    static const int on = ry_knob_int("RYOLO_W3_V8", 1);          // A/B knob: 0 = the 4-wave kernels of r03 / r04
     if (!on || p.Cin % 64) return false;
     const int nco = p.Cout <= 64 ? 2 : 4;
-    static const int pd_max = getenv("RYOLO_W3_V8_PD") ? atoi(getenv("RYOLO_W3_V8_PD")) : 2;       // A/B knob: 1 = the first cut (one step of prefetch)
+    static const int pd_max = ry_knob_int("RYOLO_W3_V8_PD", 2);       // A/B knob: 1 = the first cut (one step of prefetch)
     int pd = pd_max >= 2 ? 2 : 1, rx = 0;
     unsigned lds = 0;
     for (; pd >= 1; pd--) {                                          // two steps of prefetch where the LDS has the room (every map of the 800 x 800 step but 400 x 400)
@@ -326,17 +313,15 @@ bool w8_geometry(const WgradParams& p, W3Geom& g)
     // to HALF the chip: measured on the step (same box, alternating, img/s) 256 workgroups 879 (the 4-wave kernels at 256: 883), 192 888,
     // 160 904*, 128 894 / 908*, 96 898*, 64 891* (* = a faster box).  The side stream then owns 128 CUs at full speed and the main stream the
     // other 128 undisturbed, instead of both sharing every CU's issue slots, registers and LDS.
-    static const int max_kib = getenv("RYOLO_W3_V8_LDS") ? atoi(getenv("RYOLO_W3_V8_LDS")) : 160;
+    static const int max_kib = ry_knob_int("RYOLO_W3_V8_LDS", 160);
     if (lds > (unsigned)max_kib * 1024u) return false;
     const int gx = (int)ry_cdiv(p.Cout, 128), gc = p.Cin / 64;
-    static const int target = getenv("RYOLO_W3_V8_BLOCKS") ? atoi(getenv("RYOLO_W3_V8_BLOCKS")) : 96;
+    static const int target = ry_knob_int("RYOLO_W3_V8_BLOCKS", 96);
     int64_t sk = ry_cdiv(target, (int64_t)gx * gc);
-    static const int minsteps = getenv("RYOLO_W3_MINSTEPS") ? atoi(getenv("RYOLO_W3_MINSTEPS")) : 24;
-    const int64_t maxsplit = g.Mp / ((int64_t)minsteps * 32);
+    const int64_t maxsplit = g.Mp / ((int64_t)w3_minsteps() * 32);
     if (sk > maxsplit) sk = maxsplit;
     if (sk < 1) sk = 1;
-    static const bool force = getenv("RYOLO_W3_FORCE") != nullptr;
-    if ((int64_t)gx * gc * sk < 48 && !force) return false;           // small problems: the generic kernel's finer tiles fill the chip better
+    if ((int64_t)gx * gc * sk < 48 && !w3_force()) return false;           // small problems: the generic kernel's finer tiles fill the chip better
     g.v8 = nco;
     g.pd = pd;
     g.co64 = nco == 2 ? 1 : 0;

@@ -36,71 +36,6 @@
 
 extern __shared__ __attribute__((aligned(1024))) unsigned char ws3_lds[];
 
-// compile-time loop: hipcc does not unroll a loop whose body holds inline asm (convergent), and a rolled loop would index the register arrays
-// dynamically (they would go to scratch memory)
-template <int U, int N> struct Ws3Unroll {
-    template <class F> static __device__ __forceinline__ void run(F& f)
-    {
-        f(std::integral_constant<int, U>{});
-        Ws3Unroll<U + 1, N>::run(f);
-    }
-};
-template <int N> struct Ws3Unroll<N, N> {
-    template <class F> static __device__ __forceinline__ void run(F&) {}
-};
-
-template <int N> __device__ __forceinline__ void ws3_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-// LDS reads next to LDS-DMA in flight go through inline asm with hand-counted lgkmcnt: for a plain load hipcc's waitcnt pass cannot tell the
-// staging / patch reads from the DMA's LDS writes and drains vmcnt(0) in front of them — i.e. it would wait for the patch requested two tiles
-// ahead right after requesting it (seen in the ISA of the first cut).  LDS operations of a wave return in order, so "at most N of the
-// operations issued after X are still in flight" means X is done; scalar loads share the counter and return out of order, which can only make
-// such a wait more conservative (X cannot be outstanding while fewer than N + 1 LDS operations are).
-typedef unsigned ws3_u4 __attribute__((ext_vector_type(4)));
-typedef unsigned ws3_u2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ bf16x8 ws3_rd128(unsigned addr)
-{
-    bf16x8 r;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr) : "memory");
-    return r;
-}
-__device__ __forceinline__ ws3_u4 ws3_rd128u(unsigned addr)
-{
-    ws3_u4 r;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr) : "memory");
-    return r;
-}
-__device__ __forceinline__ ws3_u2 ws3_rd64u(unsigned addr)
-{
-    ws3_u2 r;
-    asm volatile("ds_read_b64 %0, %1" : "=v"(r) : "v"(addr) : "memory");
-    return r;
-}
-// (LDS WRITES too: in front of a plain ds_write hipcc waits for every LDS-DMA in flight — here the pieces of the patch two tiles ahead, requested
-// a few hundred cycles earlier)
-__device__ __forceinline__ void ws3_wr64(unsigned addr, unsigned lo, unsigned hi)
-{
-    const ws3_u2 v = {lo, hi};
-    asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-template <int N> __device__ __forceinline__ void ws3_wait_lds(bf16x8& f) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(f) : "n"(N)); }
-// ... and the registers of EARLIER extra reads that this wait also covers (tied, so that their consumers cannot be scheduled above it)
-template <int N> __device__ __forceinline__ void ws3_wait_lds(bf16x8& f, ws3_u2& a, ws3_u2& b, ws3_u2& c, ws3_u2& d)
-{
-    asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(f), "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
-}
-template <int N> __device__ __forceinline__ void ws3_wait_lds(bf16x8& f, ws3_u4& a, ws3_u4& b, ws3_u4& c, ws3_u4& d)
-{
-    asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(f), "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
-}
-template <int N> __device__ __forceinline__ void ws3_wait_lds(ws3_u2& a, ws3_u2& b, ws3_u2& c, ws3_u2& d)
-{
-    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
-}
-template <int N> __device__ __forceinline__ void ws3_wait_lds(ws3_u4& a, ws3_u4& b, ws3_u4& c, ws3_u4& d)
-{
-    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
-}
-
 // ---- what else rides in the MFMA shadow of a tile's 144 units (the work of the PREVIOUS tile's epilogue and of the patch two tiles ahead) ----
 //   unit 50                     accumulate epilogue: the 8 old 16-byte row segments of THIS tile are requested (consumed a tile later)
 //   units 1, 9, 17, 25          statistics: 4 staged 8-byte reads each, consumed WS3_PF units later
@@ -247,7 +182,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         lv = (m < g.TH * g.TW) & col_ok;
         return reinterpret_cast<bf16_t*>(p.out) + ((int64_t)pix0 + (lv ? r * W + c : 0)) * p.ldC + (col_ok ? ncol : 0);
     };
-    auto stat_add = [&](const ws3_u2& w) {
+    auto stat_add = [&](const ry_u2& w) {
         const float f0 = __uint_as_float(w.x << 16), f1 = __uint_as_float(w.x & 0xffff0000u);
         const float f2 = __uint_as_float(w.y << 16), f3 = __uint_as_float(w.y & 0xffff0000u);
         ssum[0] += f0; ssq[0] += f0 * f0;
@@ -255,7 +190,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         ssum[2] += f2; ssq[2] += f2 * f2;
         ssum[3] += f3; ssq[3] += f3 * f3;
     };
-    auto store_seg = [&](bf16_t* o, bool lv, const ws3_u4& sv, const uint4& old) {
+    auto store_seg = [&](bf16_t* o, bool lv, const ry_u4& sv, const uint4& old) {
         uint4 v = make_uint4(sv.x, sv.y, sv.z, sv.w);
         if (ACCUM) {
             const unsigned* a = reinterpret_cast<const unsigned*>(&v);
@@ -295,19 +230,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
             for (int e = 0; e < 16; e++) acc[b][e] = 0.f;
         bf16x8 fr[PF];
-        ws3_u2 sw[4];
-        ws3_u4 sv[4];
+        ry_u2 sw[4];
+        ry_u4 sv[4];
         bf16_t* optr[4];
         bool olv[4];
         auto rd = [&](int u) {
             const int t = u >> 4, ks = (u >> 2) & 3, b = u & 3;
-            return ws3_rd128(ks ? aaddr[b][t] ^ (unsigned)(ks << 5) : aaddr[b][t]);
+            return lds_rd128(ks ? aaddr[b][t] ^ (unsigned)(ks << 5) : aaddr[b][t]);
         };
 #ifdef WS3_TIMING
         const unsigned long long tc0 = __builtin_readcyclecounter();
 #endif
         auto pre = [&](auto uc) { constexpr int u = decltype(uc)::value; fr[u] = rd(u); };
-        Ws3Unroll<0, PF>::run(pre);
+        ry_unroll<0, PF>::run(pre);
         auto unit = [&](auto uc) {
             constexpr int u = decltype(uc)::value;
             constexpr int later = ws3_later(u, FIRST, STATS);
@@ -316,9 +251,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             // ---- wait for fragment u (and for the extra reads issued PF units ago, which precede fragment u in the LDS queue) ---------------------
             constexpr bool use_stats = !FIRST && STATS && (u == 1 + PF || u == 9 + PF || u == 17 + PF || u == 25 + PF);
             constexpr bool use_store = !FIRST && (u == 33 + PF || u == 41 + PF);
-            if constexpr (use_stats) ws3_wait_lds<later>(fr[u % PF], sw[0], sw[1], sw[2], sw[3]);
-            else if constexpr (use_store) ws3_wait_lds<later>(fr[u % PF], sv[0], sv[1], sv[2], sv[3]);
-            else ws3_wait_lds<later>(fr[u % PF]);
+            if constexpr (use_stats) lds_wait<later>(fr[u % PF], sw[0], sw[1], sw[2], sw[3]);
+            else if constexpr (use_store) lds_wait<later>(fr[u % PF], sv[0], sv[1], sv[2], sv[3]);
+            else lds_wait<later>(fr[u % PF]);
             const bf16x8 cur = fr[u % PF];
             if constexpr (use_stats) {
 #pragma unroll
@@ -349,14 +284,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             if constexpr (!FIRST && STATS && (u == 1 || u == 9 || u == 17 || u == 25)) {
                 constexpr int k4 = (u - 1) / 2;                   // rows rg + 8 (k4 + q): groups 0, 4, 8, 12
 #pragma unroll
-                for (int q = 0; q < 4; q++) sw[q] = ws3_rd64u(stg_addr8(rg + 8 * (k4 + q)));
+                for (int q = 0; q < 4; q++) sw[q] = lds_rd64u(stg_addr8(rg + 8 * (k4 + q)));
             }
             if constexpr (!FIRST && (u == 33 || u == 41)) {
                 constexpr int g0 = u == 33 ? 0 : 4;
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     optr[q] = out_ptr(prev_pix0, (g0 + q) * 16 + r0, olv[q]);
-                    sv[q] = ws3_rd128u(stg_addr16((g0 + q) * 16 + r0));
+                    sv[q] = lds_rd128u(stg_addr16((g0 + q) * 16 + r0));
                 }
             }
             if constexpr (u >= 56 && (u - 56) % 7 == 0 && (u - 56) / 7 < WS3_NPW) issue_piece((u - 56) / 7, have_far, far, bfar);
@@ -364,7 +299,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             __builtin_amdgcn_sched_barrier(0);
             acc[u & 3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wreg[u >> 4][(u >> 2) & 3], cur, acc[u & 3], 0, 0, 0);
         };
-        Ws3Unroll<0, NU>::run(unit);
+        ry_unroll<0, NU>::run(unit);
         __builtin_amdgcn_sched_barrier(0);
 #ifdef WS3_TIMING
         const unsigned long long tc1 = __builtin_readcyclecounter();
@@ -384,11 +319,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 }
                 if (!live[b]) v0 = v1 = v2 = v3 = 0.f;
                 const int row = b * 32 + l31;
-                ws3_wr64(sbase + (unsigned)(row * 64 + (((g4 ^ ((row >> 1) & 3)) << 4) | (h << 3))), pack_bf2(v0, v1), pack_bf2(v2, v3));
+                lds_wr64(sbase + (unsigned)(row * 64 + (((g4 ^ ((row >> 1) & 3)) << 4) | (h << 3))), pack_bf2(v0, v1), pack_bf2(v2, v3));
             }
         // ---- all but this tile's 12 DMA pieces have completed: the NEXT tile's patch (requested one tile ago) has landed; then everyone is done
         //      with the current buffer -----------------------------------------------------------------------------------------------------------
-        ws3_wait_vm<WS3_NPW>();
+        wait_vm<WS3_NPW>();
         __builtin_amdgcn_s_barrier();
 #ifdef WS3_TIMING
         t_tail += __builtin_readcyclecounter() - tc1;
@@ -404,7 +339,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
         for (int u = 0; u < WS3_NPW; u++) issue_piece(u, ntl > 1, t1, PB);
     }
-    ws3_wait_vm<0>();
+    wait_vm<0>();
     __builtin_amdgcn_s_barrier();
 
 #ifdef WS3_TIMING
@@ -427,10 +362,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if (STATS) {
 #pragma unroll
             for (int k4 = 0; k4 < 16; k4 += 4) {
-                ws3_u2 w[4];
+                ry_u2 w[4];
 #pragma unroll
-                for (int q = 0; q < 4; q++) w[q] = ws3_rd64u(stg_addr8(rg + 8 * (k4 + q)));
-                ws3_wait_lds<0>(w[0], w[1], w[2], w[3]);
+                for (int q = 0; q < 4; q++) w[q] = lds_rd64u(stg_addr8(rg + 8 * (k4 + q)));
+                lds_wait<0>(w[0], w[1], w[2], w[3]);
 #pragma unroll
                 for (int q = 0; q < 4; q++) stat_add(w[q]);
             }
@@ -439,13 +374,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         for (int g0 = 0; g0 < 8; g0 += 4) {
             bf16_t* o[4];
             bool lv[4];
-            ws3_u4 v[4];
+            ry_u4 v[4];
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 o[q] = out_ptr(prev_pix0, (g0 + q) * 16 + r0, lv[q]);
-                v[q] = ws3_rd128u(stg_addr16((g0 + q) * 16 + r0));
+                v[q] = lds_rd128u(stg_addr16((g0 + q) * 16 + r0));
             }
-            ws3_wait_lds<0>(v[0], v[1], v[2], v[3]);
+            lds_wait<0>(v[0], v[1], v[2], v[3]);
 #pragma unroll
             for (int q = 0; q < 4; q++) store_seg(o[q], lv[q], v[q], oldv[g0 + q]);       // (old values: requested under the last tile's MFMAs)
         }
@@ -458,7 +393,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #endif
     if (STATS) {
         // one partial row per workgroup: lanes park their 8 sums in LDS, one thread per channel folds 2 pixel halves x 8 row groups in a fixed order
-        ws3_wait_vm<0>();                                        // (the dummy DMA pieces of the last tiles: nothing may still write LDS)
+        wait_vm<0>();                                        // (the dummy DMA pieces of the last tiles: nothing may still write LDS)
         __syncthreads();
         float* part = reinterpret_cast<float*>(ws3_lds);         // [wave][rg][2][32]
         float* mine = part + ((wave * 8 + rg) * 2) * 32 + cq * 4;
@@ -486,7 +421,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // ---------------------------------------------------------------------------------------------------------- host side
 static int ws3_enabled()
 {
-    static const int v = [] { const char* e = getenv("RYOLO_P3_WS64"); return e ? atoi(e) : 1; }();
+    static const int v = ry_knob_int("RYOLO_P3_WS64", 1);
     return v;
 }
 static int ws3_cus()

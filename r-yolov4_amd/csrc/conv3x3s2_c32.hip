@@ -360,7 +360,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_c32_dgrad_kernel(const ConvG
 
 static int s2c_mode()
 {
-    static const int v = [] { const char* e = getenv("RYOLO_S2C32"); return e ? atoi(e) : 1; }();       // A/B knob: 0 = the generic 256 x 64 tile
+    static const int v = ry_knob_int("RYOLO_S2C32", 1);       // A/B knob: 0 = the generic 256 x 64 tile
     return v;
 }
 
@@ -415,7 +415,7 @@ int s2c_launch(const ConvGemmParams& p, const S2cGeom& g, hipStream_t stream)
 bool s2c_dgrad_geometry(const ConvGemmParams& p, S2cGeom& g)
 {
     g = S2cGeom{};
-    static const int on = [] { const char* e = getenv("RYOLO_S2C32_DGRAD"); return e ? atoi(e) : 1; }();   // A/B knob: 0 = the persistent pointwise kernel's S2D form
+    static const int on = ry_knob_int("RYOLO_S2C32_DGRAD", 1);   // A/B knob: 0 = the persistent pointwise kernel's S2D form
     if (!on || (p.pipe & 0xff) != 1 || !p.zeros) return false;
     if (p.s2d_cin != 32 || p.Nout != 128 || p.Cin != 64 || p.wtaps != 4 || p.nclasses != 1 || p.oh_mul != 2 || p.ow_mul != 2) return false;
     const TapClass& tc = p.cls[0];

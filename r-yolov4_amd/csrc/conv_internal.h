@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "params.h"
+#include <type_traits>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -136,6 +137,72 @@ __device__ __forceinline__ bf16x8 join_halves(ry_s16x4 lo, ry_s16x4 hi)
 template <int N> __device__ __forceinline__ void lds_wait(bf16x8& f) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(f) : "n"(N)); }
 template <int N> __device__ __forceinline__ void lds_wait2(bf16x8& f, bf16x8& g) { asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(f), "+v"(g) : "n"(N)); }
 
+// compile-time loop f(0) ... f(N - 1): hipcc does not unroll a loop whose body holds inline asm (convergent), and a rolled loop would index the
+// register arrays dynamically (they would go to scratch memory)
+template <int U, int N> struct ry_unroll {
+    template <class F> static __device__ __forceinline__ void run(F& f)
+    {
+        f(std::integral_constant<int, U>{});
+        ry_unroll<U + 1, N>::run(f);
+    }
+};
+template <int N> struct ry_unroll<N, N> {
+    template <class F> static __device__ __forceinline__ void run(F&) {}
+};
+
+template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+template <int N> __device__ __forceinline__ void wait_lgkm() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
+// Plain LDS reads next to LDS-DMA in flight go through inline asm with hand-counted lgkmcnt as well: for a plain load hipcc's waitcnt pass cannot
+// tell the staging / patch reads from the DMA's LDS writes and drains vmcnt(0) in front of them — i.e. it would wait for the patch requested two
+// tiles ahead right after requesting it (seen in the ISA of the first cut of conv3x3_ws.hip).  LDS operations of a wave return in order, so "at
+// most N of the operations issued after X are still in flight" means X is done; scalar loads share the counter and return out of order, which can
+// only make such a wait more conservative (X cannot be outstanding while fewer than N + 1 LDS operations are).
+typedef unsigned ry_u4 __attribute__((ext_vector_type(4)));
+typedef unsigned ry_u2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ bf16x8 lds_rd128(unsigned addr)
+{
+    bf16x8 r;
+    asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr) : "memory");
+    return r;
+}
+__device__ __forceinline__ ry_u4 lds_rd128u(unsigned addr)
+{
+    ry_u4 r;
+    asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr) : "memory");
+    return r;
+}
+__device__ __forceinline__ ry_u2 lds_rd64u(unsigned addr)
+{
+    ry_u2 r;
+    asm volatile("ds_read_b64 %0, %1" : "=v"(r) : "v"(addr) : "memory");
+    return r;
+}
+// (LDS WRITES too: in front of a plain ds_write hipcc waits for every LDS-DMA in flight — in conv3x3_ws.hip the pieces of the patch two tiles
+// ahead, requested a few hundred cycles earlier)
+__device__ __forceinline__ void lds_wr64(unsigned addr, unsigned lo, unsigned hi)
+{
+    const ry_u2 v = {lo, hi};
+    asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(v) : "memory");
+}
+// lds_wait<N> of a fragment and / or the registers of EARLIER extra reads that the wait also covers (tied, so that their consumers cannot be
+// scheduled above it)
+template <int N> __device__ __forceinline__ void lds_wait(bf16x8& f, ry_u2& a, ry_u2& b, ry_u2& c, ry_u2& d)
+{
+    asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(f), "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
+}
+template <int N> __device__ __forceinline__ void lds_wait(bf16x8& f, ry_u4& a, ry_u4& b, ry_u4& c, ry_u4& d)
+{
+    asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(f), "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
+}
+template <int N> __device__ __forceinline__ void lds_wait(ry_u2& a, ry_u2& b, ry_u2& c, ry_u2& d)
+{
+    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
+}
+template <int N> __device__ __forceinline__ void lds_wait(ry_u4& a, ry_u4& b, ry_u4& c, ry_u4& d)
+{
+    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
+}
+
 // bijective XCD remap (cdna guide T1): workgroup b runs on XCD b%8; give each XCD a contiguous tile range
 __device__ __forceinline__ int xcd_remap(int bid, int nwg)
 {
@@ -153,6 +220,20 @@ __device__ __forceinline__ int small_div(int n, int d, float rd)
     if ((q + 1) * d <= n) q++;
     return q;
 }
+
+// n / d == mulhi(n, m) >> s for 0 <= n < 2^31 (host side; kernels decompose pixel indices with it).  Division by one is flagged with m == 0.
+static inline void ry_magic_div(unsigned d, unsigned& m, unsigned& s)
+{
+    if (d < 2) { m = 0; s = 0; return; }
+    unsigned l = 0;
+    while ((1ull << l) < d) l++;
+    m = (unsigned)((((unsigned long long)1 << (31 + l)) + d - 1) / d);
+    s = l - 1;
+}
+
+// knobs that two translation units read (conv3x3.hip, conv3x3_wgrad8.hip): one accessor, one default
+inline int w3_minsteps() { static const int v = ry_knob_int("RYOLO_W3_MINSTEPS", 24); return v; }   // measured 24 / 48 / 128: shorter splits fill the chip, the two-halo prologue still amortises
+inline bool w3_force() { static const bool v = ry_knob_set("RYOLO_W3_FORCE"); return v; }           // A/B runs: ignore the size heuristic
 
 // ---- 3x3 stride-1 halo-patch kernel (conv3x3.hip) -------------------------------------------------------------------
 // geometry chosen on the host; `mode` 0 = not eligible, 1 = 2-D tiles (TH x TW output pixels of one image),
@@ -223,8 +304,12 @@ bool w8_geometry(const WgradParams& p, W3Geom& g);           // conv3x3_wgrad8.h
 int w8_launch(const WgradParams& p, const W3Geom& g, hipStream_t stream);
 
 // ---- pointwise weight gradient on 256 x 256 tiles, 8 waves (wgrad1x1_8w.hip): eligibility + split (what ryolo_conv_wgrad_plan reports), launch
-bool w1x8_geometry(const WgradParams& p, int* splitk, int64_t* kchunk, int* gx, int* gy);
-int w1x8_launch(const WgradParams& p, hipStream_t stream);
+struct W1x8Geom {
+    int gx, gy, splitk;
+    int64_t kchunk;
+};
+bool w1x8_geometry(const WgradParams& p, W1x8Geom& g);
+int w1x8_launch(const WgradParams& p, const W1x8Geom& g, hipStream_t stream);
 
 // ---- streaming 3x3 stride-2 forward for 32 input channels (conv3x3s2_c32.hip; r06): weights in LDS, B fragments straight from global memory --
 struct S2cGeom {

@@ -117,7 +117,7 @@ __global__ __launch_bounds__(1024) void fold_rows_kernel(const float* __restrict
 // fold_rows pass in front (A/B knob, read once)
 static int bn_fold_direct()
 {
-    static const int v = [] { const char* e = getenv("RYOLO_BN_FOLD_DIRECT"); int x = e ? atoi(e) : FOLD_DIRECT; return x < 4 * FOLD_S ? 4 * FOLD_S : x; }();
+    static const int x = ry_knob_int("RYOLO_BN_FOLD_DIRECT", FOLD_DIRECT), v = x < 4 * FOLD_S ? 4 * FOLD_S : x;
     return v;
 }
 static inline const float* fold_rows(const float* partial, int& rows, int KC, float* scratch, hipStream_t stream)
@@ -1465,8 +1465,8 @@ static inline unsigned grid_rows(int64_t M, int C)
     // over the whole tensor; workgroups that each finish after 4 rows keep them inside a window that moves through memory in dispatch order:
     // forward 5.0-5.5 -> 6.2 TB/s, backward apply 5.1-5.7 -> 6.3-7.0 TB/s isolated (tools/bench_bnact.py; 2 rows: same forward, apply -6 %;
     // 1 row: apply 4.5 TB/s; 8 rows: -3 %).  RYOLO_EW_GRID / RYOLO_EW_ROWS: A/B knobs.
-    static const int cap = getenv("RYOLO_EW_GRID") ? atoi(getenv("RYOLO_EW_GRID")) : (1 << 20);
-    static const int rpt = getenv("RYOLO_EW_ROWS") ? atoi(getenv("RYOLO_EW_ROWS")) : 4;
+    static const int cap = ry_knob_int("RYOLO_EW_GRID", (1 << 20));
+    static const int rpt = ry_knob_int("RYOLO_EW_ROWS", 4);
     int64_t g = ry_cdiv(M, (int64_t)rpi * rpt);
     if (g > cap) g = cap;
     if (g < 1) g = 1;
@@ -1474,7 +1474,7 @@ static inline unsigned grid_rows(int64_t M, int C)
 }
 static inline unsigned grid_for(int64_t work_items)
 {
-    static const int cap = getenv("RYOLO_EW_GRID2") ? atoi(getenv("RYOLO_EW_GRID2")) : 8192;     // A/B knob
+    static const int cap = ry_knob_int("RYOLO_EW_GRID2", 8192);     // A/B knob
     int64_t g = ry_cdiv(work_items, 256);
     if (g > cap) g = cap;
     if (g < 1) g = 1;
@@ -1564,7 +1564,7 @@ extern "C" int ryolo_bn_act_bwd_blocks(int64_t M, int C, int* nblk, int* rows_pe
     // 1280 = 5 resident workgroups x 256 CUs: one round of workgroups, each walking one contiguous run of rows, and a third of the partial rows
     // for the finalize kernel (r04 kernel, same box, alternating runs: 856 img/s at 1280 vs 853 at 4096 / 2560 / 2048, 850 at 640; with the r02
     // kernel — 3 waves per SIMD, no read-ahead — 2048 blocks had been 3 ms/step slower than 4096).  RYOLO_BN_RED_BLOCKS: A/B knob.
-    static const int cap = getenv("RYOLO_BN_RED_BLOCKS") ? atoi(getenv("RYOLO_BN_RED_BLOCKS")) : 1280;
+    static const int cap = ry_knob_int("RYOLO_BN_RED_BLOCKS", 1280);
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     *rows_per_block = (int)ry_cdiv(M, blocks);
@@ -1724,7 +1724,7 @@ static int head_finish_bwd_impl(const float* dout, const float* pre, int ldp, co
     const int TC = head_tile_cells(C);
     const size_t lds = ((size_t)TC * (C + 1) + C) * sizeof(float);
     // (with four quads per thread compiled in for every C the kernel held 179 VGPRs = 2 waves per SIMD)
-    static const int direct = getenv("RYOLO_HEAD_SPARSE_DIRECT") ? atoi(getenv("RYOLO_HEAD_SPARSE_DIRECT")) : 1;      // 0: the dense kernel's sparse tile fill (what larger heads take)
+    static const int direct = ry_knob_int("RYOLO_HEAD_SPARSE_DIRECT", 1);      // 0: the dense kernel's sparse tile fill (what larger heads take)
     if (objgrad && direct && C <= 512 && na <= HS_MAXNA && (preobj || !mul)) {
         const size_t l2 = ((size_t)na * 2 * HS_LDA + 5 * C + 1) * sizeof(float) + (size_t)na * 2 * sizeof(unsigned long long);
         hipLaunchKernelGGL(head_bwd_sparse_kernel, dim3(rows), dim3(256), l2, stream, dout, objgrad, preobj, owner, och, pre, ldp, mul, B, gs, na, attrs,

@@ -22,8 +22,6 @@
 #define WS_STG 3                  // ring stages per wave: [64 px][32 ch] bf16 = 4 KiB each
 #define WS_RING (WS_STG * WS_TM * 32)      // elements per wave
 
-template <int N> __device__ __forceinline__ void ws_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 // S2D instantiations: the space-to-depth form of a stride-2 3x3 data gradient with 32 input channels (ConvGemmParams.s2d_cin == 32: ONE
 // stride-1 GEMM over the dY grid, 2 x 2 taps, Nout = 4 parity blocks x 32 channels — the second layer of every backbone, the slowest launch of
 // the step on the generic kernel: 8-16 K steps that re-fetch a 64 KiB weight tile per 128 pixels).  K step k is (tap, 32-channel chunk):
@@ -65,7 +63,7 @@ __global__ __launch_bounds__(512, 1) void gemm1x1_ws_kernel(const ConvGemmParams
     bf16_t* ring = smem + nk * (WS_BN * 32) + wave * WS_RING;
     const bf16_t* abase = p.A + (int64_t)(lane >> 2) * p.ldA + (((lane & 3) ^ swz) << 3);
     const int64_t qoff = (int64_t)16 * p.ldA;
-    ws_wait_vm<0>();
+    wait_vm<0>();
     __syncthreads();                                               // the only workgroup barrier of the launch
 
     const int h = lane >> 5, l31 = lane & 31;
@@ -141,10 +139,10 @@ __global__ __launch_bounds__(512, 1) void gemm1x1_ws_kernel(const ConvGemmParams
 #pragma unroll
                     for (int e = 0; e < 16; e++) acc[i][j][e] = 0.f;
             for (int k = 0; k < nk; k++) {
-                if (k == nk - 1 && !has_next) ws_wait_vm<0>();      // the wave's very last stage: nothing newer was issued
-                else if (!first && k < 2 && full_n) ws_wait_vm<4 + 16>();   // newer than my stage: the next stage and the previous epilogue's 16 stores
+                if (k == nk - 1 && !has_next) wait_vm<0>();      // the wave's very last stage: nothing newer was issued
+                else if (!first && k < 2 && full_n) wait_vm<4 + 16>();   // newer than my stage: the next stage and the previous epilogue's 16 stores
                                                                     // (a ragged n tile may skip whole quarters' stores: it waits for them too, which is always safe)
-                else ws_wait_vm<4>();
+                else wait_vm<4>();
                 const bf16_t* sa = ring + cur * (WS_TM * 32);
                 const bf16_t* sb = smem + k * (WS_BN * 32);
                 bf16x8 af[2][2], bfr[2][4];
@@ -385,15 +383,17 @@ static int ws_mode()
 {
     // on by size since the end of r04: with 512 / 256 weight-gradient workgroups on the side stream (conv.hip, conv3x3.hip) the step gains 0.25 %
     // from it (three alternating same-box comparisons); with 768 / 512 it lost 0.4 % (above)
-    static const int m = getenv("RYOLO_GEMM_WS") ? atoi(getenv("RYOLO_GEMM_WS")) : 1;
+    static const int m = ry_knob_int("RYOLO_GEMM_WS", 1);
     return m;
 }
+
+static int ws_wgs() { static const int v = ry_knob_int("RYOLO_GEMM_WS_WGS", 256); return v; }     // one workgroup per CU
 
 static bool ws1_geometry_1x1(const ConvGemmParams& p, Ws1Geom& g);
 // the space-to-depth data gradient of a 32-input-channel stride-2 layer (see WsTaps): RYOLO_GEMM_WS_S2D = 0 keeps it on the generic kernel
 static bool ws1_s2d_eligible(const ConvGemmParams& p)
 {
-    static const bool on = !(getenv("RYOLO_GEMM_WS_S2D") && atoi(getenv("RYOLO_GEMM_WS_S2D")) == 0);
+    static const bool on = ry_knob_int("RYOLO_GEMM_WS_S2D", 1) != 0;
     if (!on || p.s2d_cin != 32 || p.Nout != 128 || p.nclasses != 1 || p.oh_mul != 2 || p.ow_mul != 2 || p.cls[0].oh_add || p.cls[0].ow_add) return false;
     const int nt = p.cls[0].ntaps;
     if (nt < 1 || nt > 4 || p.Cin % 32 || nt * (p.Cin / 32) > 8 || nt * (p.Cin / 32) < 2) return false;
@@ -409,7 +409,7 @@ bool ws1_geometry(const ConvGemmParams& p, Ws1Geom& g)
     g.s2d = 0;
     if ((p.pipe & 0xff) == 1 && p.zeros && ws1_s2d_eligible(p)) {
         const int64_t tiles = ry_cdiv((int64_t)p.NB * p.OH * p.OW, WS_TM);
-        static const int cus = getenv("RYOLO_GEMM_WS_WGS") ? atoi(getenv("RYOLO_GEMM_WS_WGS")) : 256;
+        const int cus = ws_wgs();
         g.nk = p.cls[0].ntaps * (p.Cin / 32);
         g.gridN = 1;
         g.wgn = (int)(tiles < (int64_t)cus * WS_WAVES ? ry_cdiv(tiles, WS_WAVES) : cus);
@@ -427,7 +427,7 @@ static bool ws1_geometry_1x1(const ConvGemmParams& p, Ws1Geom& g)
     g.ok = 0;
     g.pool = 0;
     // pointwise data gradients with a fused MaxPool gradient run here by default (RYOLO_GEMM_WS_POOL = 0: generic kernel); plain ones by RYOLO_GEMM_WS
-    static const bool pool_on = !(getenv("RYOLO_GEMM_WS_POOL") && atoi(getenv("RYOLO_GEMM_WS_POOL")) == 0);
+    static const bool pool_on = ry_knob_int("RYOLO_GEMM_WS_POOL", 1) != 0;
     const bool pool = p.pool_idx != nullptr;
     if (pool && (!pool_on || !p.pool_dz || p.pool_ld % 8 || p.pool_ldi % 8 || (p.OH & 1) || (p.OW & 1) || (p.epi != EPI_RAW && p.epi != EPI_ACCUM) ||
                  (int64_t)p.NB * p.OH * p.OW >= (1ll << 31)))
@@ -443,7 +443,7 @@ static bool ws1_geometry_1x1(const ConvGemmParams& p, Ws1Geom& g)
     const int64_t tiles = ry_cdiv(M, WS_TM);
     g.nk = p.Cin / 32;
     g.gridN = (int)ry_cdiv(p.Nout, WS_BN);
-    static const int cus = getenv("RYOLO_GEMM_WS_WGS") ? atoi(getenv("RYOLO_GEMM_WS_WGS")) : 256;     // one workgroup per CU
+    const int cus = ws_wgs();
     if (g.gridN > cus) return false;
     g.wgn = cus / g.gridN;
     if (tiles < (int64_t)g.wgn * WS_WAVES) {                       // fewer tiles than waves: shrink the grid (forced mode), else not eligible
@@ -461,16 +461,9 @@ int ws1_launch(const ConvGemmParams& p, const Ws1Geom& g, hipStream_t stream)
 {
     static RyLdsAttr attr[8];
     WsTaps tk = {};
-    auto magic = [](unsigned d, unsigned& m, unsigned& sh) {         // n / d == mulhi(n, m) >> sh for 0 <= n < 2^31 (m == 0: d == 1)
-        if (d < 2) { m = 0; sh = 0; return; }
-        unsigned l = 0;
-        while ((1ull << l) < d) l++;
-        m = (unsigned)((((unsigned long long)1 << (31 + l)) + d - 1) / d);
-        sh = l - 1;
-    };
     if (g.s2d || g.pool) {
-        magic((unsigned)(p.OH * p.OW), tk.m_img, tk.s_img);
-        magic((unsigned)p.OW, tk.m_row, tk.s_row);
+        ry_magic_div((unsigned)(p.OH * p.OW), tk.m_img, tk.s_img);
+        ry_magic_div((unsigned)p.OW, tk.m_row, tk.s_row);
     }
     if (g.s2d) {
         const TapClass& tc = p.cls[0];

@@ -28,42 +28,6 @@
 
 extern __shared__ __attribute__((aligned(1024))) unsigned char g256_lds[];
 
-template <int U, int N> struct G256Unroll {
-    template <class F> static __device__ __forceinline__ void run(F& f)
-    {
-        f(std::integral_constant<int, U>{});
-        G256Unroll<U + 1, N>::run(f);
-    }
-};
-template <int N> struct G256Unroll<N, N> {
-    template <class F> static __device__ __forceinline__ void run(F&) {}
-};
-template <int N> __device__ __forceinline__ void g256_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ bf16x8 g256_rd128(unsigned addr)
-{
-    bf16x8 r;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr) : "memory");
-    return r;
-}
-typedef unsigned g256_u4 __attribute__((ext_vector_type(4)));
-typedef unsigned g256_u2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ g256_u4 g256_rd128u(unsigned addr)
-{
-    g256_u4 r;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr) : "memory");
-    return r;
-}
-__device__ __forceinline__ g256_u2 g256_rd64u(unsigned addr)
-{
-    g256_u2 r;
-    asm volatile("ds_read_b64 %0, %1" : "=v"(r) : "v"(addr) : "memory");
-    return r;
-}
-__device__ __forceinline__ void g256_wr64(unsigned addr, unsigned lo, unsigned hi)
-{
-    const g256_u2 v = {lo, hi};
-    asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
 // all LDS operations of this wave have completed; the fragments named are usable from here on
 template <int NF> __device__ __forceinline__ void g256_wait_lds0(bf16x8 (&f)[NF])
 {
@@ -71,14 +35,6 @@ template <int NF> __device__ __forceinline__ void g256_wait_lds0(bf16x8 (&f)[NF]
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]));
     else
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]));
-}
-__device__ __forceinline__ void g256_wait_lds0(g256_u4& a, g256_u4& b, g256_u4& c, g256_u4& d)
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-}
-__device__ __forceinline__ void g256_wait_lds0(g256_u2& a, g256_u2& b, g256_u2& c, g256_u2& d)
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
 }
 
 // BN = 256: wave tile 128 pixels x 64 channels (TN = 2 channel blocks); BN = 128: 128 x 32 (TN = 1)
@@ -168,16 +124,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #endif
     for (int k = 0; k < nk; k++) {
         const unsigned soff = (k & 1) ? STAGE : 0u;
-        g256_wait_vm<0>();                                      // my pieces of step k (requested a whole step ago) have landed ...
+        wait_vm<0>();                                      // my pieces of step k (requested a whole step ago) have landed ...
         __builtin_amdgcn_s_barrier();                           // ... everyone's have, and everyone is done with step k - 1
         unsigned sb = lbase + soff;
         asm volatile("" : "+v"(sb));                            // (opaque: keeps the 4 x NF fragment addresses of a step out of loop-invariant registers)
         bf16x8 fr[2][NF];
         auto rd_set = [&](int ks, bf16x8 (&f)[NF]) {
 #pragma unroll
-            for (int i = 0; i < 4; i++) f[i] = g256_rd128(sb + (pa[i] ^ (unsigned)(ks << 5)));
+            for (int i = 0; i < 4; i++) f[i] = lds_rd128(sb + (pa[i] ^ (unsigned)(ks << 5)));
 #pragma unroll
-            for (int j = 0; j < TN; j++) f[4 + j] = g256_rd128(sb + (wa[j] ^ (unsigned)(ks << 5)));
+            for (int j = 0; j < TN; j++) f[4 + j] = lds_rd128(sb + (wa[j] ^ (unsigned)(ks << 5)));
         };
         rd_set(0, fr[0]);                                       // first fragments requested BEFORE the next stage's DMA is issued: their LDS latency
         __builtin_amdgcn_sched_barrier(0);                      // runs under the ~70 address / M0 / DMA instructions below
@@ -194,7 +150,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 for (int j = 0; j < TN; j++)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[ks & 1][4 + j], fr[ks & 1][i], acc[i][j], 0, 0, 0);
         };
-        G256Unroll<0, 4>::run(sub);
+        ry_unroll<0, 4>::run(sub);
         __builtin_amdgcn_sched_barrier(0);
     }
 #ifdef G256_TIMING
@@ -222,7 +178,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     const float sc4[4] = {sc.x, sc.y, sc.z, sc.w}, sf4[4] = {sh.x, sh.y, sh.z, sh.w};
                     act_affine_quad(v, sc4, sf4, p.act);
                 }
-                g256_wr64(sbase + (unsigned)row * ROWB + (unsigned)(((chunk ^ (row & (CHK - 1))) << 4) | (h << 3)),
+                lds_wr64(sbase + (unsigned)row * ROWB + (unsigned)(((chunk ^ (row & (CHK - 1))) << 4) | (h << 3)),
                           pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
             }
     // (wave-local hand-off: the wave's own LDS operations are ordered)
@@ -238,13 +194,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         // rows past M hold exact zeros (zero-page operands), columns past Nout likewise
 #pragma unroll
         for (int k4 = 0; k4 < 128 / RGS; k4 += 4) {
-            g256_u2 w[4];
+            ry_u2 w[4];
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 const int row = rg + RGS * (k4 + q);
-                w[q] = g256_rd64u(sbase + (unsigned)row * ROWB + (unsigned)((((cq >> 1) ^ (row & (CHK - 1))) << 4) | ((cq & 1) << 3)));
+                w[q] = lds_rd64u(sbase + (unsigned)row * ROWB + (unsigned)((((cq >> 1) ^ (row & (CHK - 1))) << 4) | ((cq & 1) << 3)));
             }
-            g256_wait_lds0(w[0], w[1], w[2], w[3]);
+            lds_wait<0>(w[0], w[1], w[2], w[3]);
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 const float f0 = __uint_as_float(w[q].x << 16), f1 = __uint_as_float(w[q].x & 0xffff0000u);
@@ -261,7 +217,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         bf16_t* optr[4];
         bool lv[4];
         uint4 oldv[4];
-        g256_u4 sv[4];
+        ry_u4 sv[4];
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const int row = (g0 + q) * RPI + r0;
@@ -269,9 +225,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             lv[q] = (m < M) & col_ok;
             optr[q] = reinterpret_cast<bf16_t*>(p.out) + (lv[q] ? m : m0) * p.ldC + (col_ok ? ncol : n0);
             if (ACCUM) oldv[q] = *reinterpret_cast<const uint4*>(optr[q]);
-            sv[q] = g256_rd128u(sbase + (unsigned)row * ROWB + (unsigned)((ch ^ (row & (CHK - 1))) << 4));
+            sv[q] = lds_rd128u(sbase + (unsigned)row * ROWB + (unsigned)((ch ^ (row & (CHK - 1))) << 4));
         }
-        g256_wait_lds0(sv[0], sv[1], sv[2], sv[3]);
+        lds_wait<0>(sv[0], sv[1], sv[2], sv[3]);
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             uint4 v = make_uint4(sv[q].x, sv[q].y, sv[q].z, sv[q].w);
@@ -323,7 +279,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // ---------------------------------------------------------------------------------------------------------- host side
 static int g256_mode()
 {
-    static const int v = [] { const char* e = getenv("RYOLO_GEMM_256"); return e ? atoi(e) : 1; }();      // 0 off, 1 by size, 2 every eligible launch (tests)
+    static const int v = ry_knob_int("RYOLO_GEMM_256", 1);      // 0 off, 1 by size, 2 every eligible launch (tests)
     return v;
 }
 
@@ -349,7 +305,7 @@ bool g256_geometry(const ConvGemmParams& p, G256Geom& g)
         // least ~2.4 rounds of one workgroup per CU (a 256-wide tile on a 1.2-round grid idles half the chip in its second round)
         // (and 256-column tiles only: the 256 x 128 form measured 443 TF/s on 512 -> 128 @100^2 against 487 on the generic kernel — half the MFMAs
         // per barrier for the same pixel stream; it stays reachable with RYOLO_GEMM_256=2 for the tests)
-        static const int mink = [] { const char* e = getenv("RYOLO_GEMM_256_MINK"); return e ? atoi(e) : 512; }();      // A/B knob
+        static const int mink = ry_knob_int("RYOLO_GEMM_256_MINK", 512);      // A/B knob
         if (p.Cin < mink || g.gm * g.gn < 600 || g.BN != 256) return false;
     }
     g.lds_bytes = 2u * (256u + (unsigned)g.BN) * 128u + (p.epi == EPI_AFFINE_ACT ? 2u * (unsigned)g.BN * 4u : 0u);

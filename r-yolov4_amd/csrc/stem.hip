@@ -787,7 +787,7 @@ __global__ __launch_bounds__(1024) void stem_bwd_finalize_kernel(const float* __
 static int stem_blocks(int64_t M) { const int64_t t = ry_cdiv(M, 32 * 4 * 8); return (int)(t > 2048 ? 2048 : (t < 1 ? 1 : t)); }
 // LDS-patch kernels: the grid is what is resident at once (256 CUs x up to 4 workgroups), every wave walks its tiles with a prefetch
 static int stem_lds_blocks(int64_t M, int per_cu = 4) { const int64_t t = ry_cdiv(M, 32 * 4 * 2), cap = 256 * per_cu; return (int)(t > cap ? cap : (t < 1 ? 1 : t)); }
-static bool stem_no_lds() { static const bool v = getenv("RYOLO_STEM_NO_LDS") != nullptr; return v; }   // A/B: the register-gather forward
+static bool stem_no_lds() { static const bool v = ry_knob_set("RYOLO_STEM_NO_LDS"); return v; }   // A/B: the register-gather forward
 
 static bool stem_ok(int NB, int H, int W, int Cout)
 {

@@ -21,14 +21,6 @@
 
 extern __shared__ __attribute__((aligned(1024))) unsigned char w1x8_lds[];
 
-template <int K> __device__ __forceinline__ void w1x8_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K) : "memory"); }
-template <int N> __device__ __forceinline__ void w1x8_wait_lgkm() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
-
-struct W1x8Geom {
-    int gx, gy, splitk;
-    int64_t kchunk;
-};
-
 __global__ __launch_bounds__(512, 1) void wgrad1x1_8w_kernel(const WgradParams p, const W1x8Geom g)
 {
     constexpr int OPB = 64 * 512;                                    // bytes of one operand in a stage: [64 px][512 B]
@@ -98,7 +90,7 @@ __global__ __launch_bounds__(512, 1) void wgrad1x1_8w_kernel(const WgradParams p
             for (int e = 0; e < 16; e++) acc[i][j][e] = 0.f;
 
     for (int s = 0; s < nk; s++) {
-        w1x8_wait_vm<0>();                                            // everything this wave requested one step ago has landed
+        wait_vm<0>();                                            // everything this wave requested one step ago has landed
         __builtin_amdgcn_s_barrier();                                 // ... and everybody else's; step s - 1 fully consumed
         const bool more = s + 1 < nk;
         const unsigned sb = (unsigned)((s & 1) * STB);
@@ -137,7 +129,7 @@ __global__ __launch_bounds__(512, 1) void wgrad1x1_8w_kernel(const WgradParams p
             constexpr bool last = ks == 3;
             __builtin_amdgcn_sched_barrier(0);
             // in flight here: the 12 reads of slice ks.  First 8 landed <=> at most 4 outstanding.
-            w1x8_wait_lgkm<4>();
+            wait_lgkm<4>();
             asm volatile("" : "+v"(al[ks & 1][0]), "+v"(ah[ks & 1][0]), "+v"(al[ks & 1][1]), "+v"(ah[ks & 1][1]));
             asm volatile("" : "+v"(bl[ks & 1][0]), "+v"(bh[ks & 1][0]), "+v"(bl[ks & 1][1]), "+v"(bh[ks & 1][1]));
             __builtin_amdgcn_sched_barrier(0);
@@ -150,7 +142,7 @@ __global__ __launch_bounds__(512, 1) void wgrad1x1_8w_kernel(const WgradParams p
             for (int i = 0; i < 4; i++) {
                 if (i == 2) {
                     __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (!last) w1x8_wait_lgkm<8>(); else w1x8_wait_lgkm<0>();     // dY blocks 2, 3 of slice ks (issued before the 8 of slice ks + 1)
+                    if constexpr (!last) wait_lgkm<8>(); else wait_lgkm<0>();     // dY blocks 2, 3 of slice ks (issued before the 8 of slice ks + 1)
                     asm volatile("" : "+v"(al[ks & 1][2]), "+v"(ah[ks & 1][2]), "+v"(al[ks & 1][3]), "+v"(ah[ks & 1][3]));
                     __builtin_amdgcn_sched_barrier(0);
                     if constexpr (!last) read_second(std::integral_constant<int, ks + 1>{}); // 8 + 4 in flight
@@ -196,40 +188,37 @@ __global__ __launch_bounds__(512, 1) void wgrad1x1_8w_kernel(const WgradParams p
     }
 }
 
-// eligibility + grid of the 8-wave pointwise form; *splitk / *kchunk as ryolo_conv_wgrad_plan reports them.  false: the 4-wave kernels of conv.hip.
-bool w1x8_geometry(const WgradParams& p, int* splitk, int64_t* kchunk, int* gx_out, int* gy_out)
+// eligibility + grid of the 8-wave pointwise form; g.splitk / g.kchunk as ryolo_conv_wgrad_plan reports them.  false: the 4-wave kernels of conv.hip.
+bool w1x8_geometry(const WgradParams& p, W1x8Geom& g)
 {
-    static const int on = getenv("RYOLO_WGRAD_8W") ? atoi(getenv("RYOLO_WGRAD_8W")) : 1;       // A/B knob
+    static const int on = ry_knob_int("RYOLO_WGRAD_8W", 1);       // A/B knob
     if (!on || !p.zeros) return false;
     if (p.ntaps != 1 || p.dh[0] != 0 || p.dw[0] != 0 || p.sh != 1 || p.sw != 1 || p.IH != p.OH || p.IW != p.OW) return false;
     // Cin >= 256 and Cout > 128 by default.  Narrower layers (down to 128 channels: RYOLO_WGRAD_8W_MINC=128) run correctly with idle waves (`active`
     // in the kernel; tests/test_gpu_wgrad1x1.py forces it) but cost the step 1 % (same box, three alternating runs: 905.9 vs 894.4 img/s): their
     // 4-wave launches are short, HBM-bound and overlap well as they are.
-    static const int min_c = getenv("RYOLO_WGRAD_8W_MINC") ? atoi(getenv("RYOLO_WGRAD_8W_MINC")) : 256;
+    static const int min_c = ry_knob_int("RYOLO_WGRAD_8W_MINC", 256);
     if (p.Cin < min_c || p.Cin % 32 || p.Cout <= min_c / 2) return false;
     if (p.ldX % 8 || p.ldY % 8 || p.CoutPad % 8 || ((reinterpret_cast<uintptr_t>(p.dY) | reinterpret_cast<uintptr_t>(p.X)) & 15)) return false;
     const int64_t M = (int64_t)p.NB * p.OH * p.OW;
     if (M >= (1ll << 31) || M < 64) return false;
     const int gx = (int)ry_cdiv(p.Cout, 256), gy = (int)ry_cdiv(p.Cin, 256);
-    static const int target = getenv("RYOLO_WGRAD_8W_BLOCKS") ? atoi(getenv("RYOLO_WGRAD_8W_BLOCKS")) : 96;
+    static const int target = ry_knob_int("RYOLO_WGRAD_8W_BLOCKS", 96);
     int64_t sk = ry_cdiv(target, (int64_t)gx * gy);
     const int64_t maxsplit = ry_cdiv(M, 16 * 64);                     // at least 16 steps per split
     if (sk > maxsplit) sk = maxsplit;
     if (sk < 1) sk = 1;
-    static const bool force = getenv("RYOLO_WGRAD_8W_FORCE") != nullptr;
+    static const bool force = ry_knob_set("RYOLO_WGRAD_8W_FORCE");
     if ((int64_t)gx * gy * sk < 48 && !force) return false;
-    const int64_t kc = ry_cdiv(ry_cdiv(M, sk), 64) * 64;
-    *kchunk = kc;
-    *splitk = (int)ry_cdiv(M, kc);
-    *gx_out = gx;
-    *gy_out = gy;
+    g.kchunk = ry_cdiv(ry_cdiv(M, sk), 64) * 64;
+    g.splitk = (int)ry_cdiv(M, g.kchunk);
+    g.gx = gx;
+    g.gy = gy;
     return true;
 }
 
-int w1x8_launch(const WgradParams& p, hipStream_t stream)
+int w1x8_launch(const WgradParams& p, const W1x8Geom& g, hipStream_t stream)
 {
-    W1x8Geom g;
-    if (!w1x8_geometry(p, &g.splitk, &g.kchunk, &g.gx, &g.gy)) return RY_ERR_ARG;
     static RyLdsAttr attr;
     if (ry_max_dynamic_lds(attr, reinterpret_cast<const void*>(&wgrad1x1_8w_kernel), 160 * 1024)) return RY_ERR_LAUNCH;
     const dim3 grid((unsigned)((int64_t)g.gx * g.gy * g.splitk));
