@@ -344,6 +344,33 @@ int ryolo_tile_cut(const uint8_t* pool, const int64_t* win, int64_t win0, int co
  * and windows at or past nwin: zero rows, -inf keys.  (win0 + batch) * mk <= ld. */
 int ryolo_tile_collect(const float* dets, const int32_t* num, int batch, int64_t mk, const float* geom, int64_t win0, int64_t nwin, int nc,
                        int64_t ld, float* cand, float* key, float* fkey, ryolo_stream_t stream);
+/* Flip / 90-degree views of a window (test-time orientation ensembling; lib/tiled.py VIEWS).  With win the S x S x 3 window
+ * ryolo_tile_cut sees (114 outside the scene: the fill turns with the window) and continuous coordinates (pixel i covers [i, i + 1)):
+ *   code  name           pixels (numpy)                        view point (x, y) -> window point   theta' before the wrap
+ *   0     id             win                                   (x, y)                              theta (bits unchanged)
+ *   1     hflip          win[:, ::-1]                          (S - x, y)                          -theta
+ *   2     vflip          win[::-1]                             (x, S - y)                          -theta
+ *   3     rot180         win[::-1, ::-1]                       (S - x, S - y)                      theta (bits unchanged)
+ *   4     transpose      win.transpose(1, 0, 2)                (y, x)                              pi/2 - theta
+ *   5     rot90          np.rot90(win, 1)                      (S - y, x)                          theta + pi/2
+ *   6     rot270         np.rot90(win, 3)                      (y, S - x)                          theta - pi/2
+ *   7     antitranspose  np.rot90(win, 2).transpose(1, 0, 2)   (S - y, S - x)                      pi/2 - theta
+ * w and h are carried over unchanged (h stays the long side).  For the six codes that change theta, theta' goes once through norm_angle's
+ * two selects (lib/general.py:14-15): >= pi/2 -> subtract pi, then < -pi/2 -> add pi; fp32 with (float)pi/2 and (float)pi, one
+ * operation per step.
+ *
+ * ryolo_tile_cut with the window table win int64 [nwin][6] = (ryolo_tile_cut's five columns, view code): slot k of dst holds view
+ * `code` of window win0 + k as RGB / 255.  Same contract otherwise (pool + byte offset at any alignment, S % 4 == 0, slots >= count are
+ * not touched, no intermediate canvas).  Codes 0-3 are index arithmetic (a reversed row is read forward and reversed in registers);
+ * codes 4-7 turn 32 x 32 pixel tiles through LDS.  The table lives on the device and the call does not read it back: a row whose code
+ * is outside 0-7 leaves its slot untouched (lib/tiled.py validates the names it encodes). */
+int ryolo_tile_cut_views(const uint8_t* pool, const int64_t* win, int64_t win0, int count, int S, float* dst, ryolo_stream_t stream);
+/* ryolo_tile_collect for entries seen through a view: geom fp32 [nwin][4] = (x0, y0, rate, view code), S the window size.  The row
+ * of a detection (x, y, w, h, theta, score, cls) is mapped to its window point and theta' by the table above, then shifted as
+ * ryolo_tile_collect does: ((px + x0) / rate, (py + y0) / rate, w / rate, h / rate, theta', score, cls).  Every slot of the group is
+ * written exactly once (an entry whose code is outside 0-7 as empty slots); no atomics, deterministic. */
+int ryolo_tile_collect_views(const float* dets, const int32_t* num, int batch, int64_t mk, const float* geom, int64_t win0, int64_t nwin,
+                             int nc, int64_t ld, int S, float* cand, float* key, float* fkey, ryolo_stream_t stream);
 /* skey / order [nc, K] = ryolo_topk_desc of key -> rboxes [nc, K, 5] = (x, y, w, h, theta degrees) of the selected candidates in scene
  * pixels, no class offset (zero rows for -inf entries): the input of ryolo_nms_rotated_batched with batch = nc. */
 int ryolo_tile_merge_gather(const float* cand, const float* skey, const int64_t* order, int nc, int64_t K, float* rboxes, ryolo_stream_t stream);

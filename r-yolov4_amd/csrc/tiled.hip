@@ -5,9 +5,12 @@
 //   tile_cut_kernel      uint8 HWC BGR scene (pool base + byte offset) -> the graph's static input fp32 [B,3,S,S] as RGB / 255, 114 / 255
 //                        outside the scene; one launch per window group.  Bit-identical to ryolo_paste_rects(fill=114) + ryolo_to_tensor
 //                        (the chain it replaces) without their intermediate canvas.
+//   tile_cut_views_kernel  the same cut with the window written in one of the eight flip / 90-degree views (view code per table row); the
+//                        four transposing views turn a 32 x 32 pixel tile through LDS.
 //   tile_collect_kernel  dets [B,mk,7] / num [B] of a group -> candidate rows in scene coordinates at the fixed slot window * mk + j and the
 //                        per-class key rows key [nc][ld] (score in the row of the box's class, -inf elsewhere); every slot of the group is
 //                        written exactly once (no fill pass, no atomics: deterministic).
+//   tile_collect_views_kernel  the same with the view's inverse map (point and angle) in front of the shift.
 //   (ryolo_topk_desc over the nc key rows)
 //   tile_gather_kernel   per-class top-K slots -> NMS boxes [nc,K,5] in scene pixels, theta in degrees, NO class offset: the per-image path
 //                        separates classes by cls * 4096 px (lib/general.py:14), which collides on scenes wider than 4096 px; here a
@@ -132,6 +135,162 @@ __global__ __launch_bounds__(256) void tile_emit_kernel(const float* __restrict_
     }
 }
 
+// ------------------------------------------------------------------------------------------ flip / 90-degree views
+// View codes (include/ryolo.h): 0 id, 1 hflip, 2 vflip, 3 rot180, 4 transpose, 5 rot90, 6 rot270, 7 antitranspose.  With `win` the
+// S x S window tile_cut_kernel produces (114 outside the scene: the fill turns with the window), view pixel (y, x) is
+//   codes 0-3:  win[fy ? S-1-y : y][fx ? S-1-x : x]     fx = code & 1, fy = code & 2
+//   codes 4-7:  win[fr ? S-1-x : x][fc ? S-1-y : y]     fc = code == 5 || code == 7, fr = code == 6 || code == 7
+// window table rows (int64 [nwin][6]): the five columns of TW_ROW and the view code
+#define TV_ROW 6
+#define TV_TILE 32
+#define TV_PITCH 33
+
+// 4 consecutive pixels of a window row as 12 BGR bytes packed in 3 dwords (byte n of the 12 = TV_BYTE(q, n)), 114 outside the H x W
+// source: tile_cut_kernel's read
+#define TV_BYTE(q, n) (((q)[(n) >> 2] >> (8 * ((n) & 3))) & 255u)
+__device__ __forceinline__ void tv_load4(const uint8_t* __restrict__ src, int H, int W, int sy, int sx, uint32_t* q)
+{
+    if (sy < H && sx + 4 <= W) {
+        __builtin_memcpy(q, src + ((int64_t)sy * W + sx) * 3, 12);
+    } else {
+        q[0] = q[1] = q[2] = 0x72727272u;                               // 114 in every byte
+        if (sy < H) {
+            const uint8_t* sp = src + ((int64_t)sy * W + sx) * 3;
+#pragma unroll
+            for (int n = 0; n < 12; n++)
+                if (sx + n / 3 < W) q[n >> 2] = (q[n >> 2] & ~(255u << (8 * (n & 3)))) | (uint32_t)sp[n] << (8 * (n & 3));
+        }
+    }
+}
+
+// One block = one window (blockIdx.y) and 256 threads x 4 output pixels; every thread reads 12 contiguous source bytes along a source
+// row and stores one float4 per colour plane along an output row, whatever the view.
+//   codes 0-3: tile_cut_kernel's linear mapping (a block = 1024 consecutive output pixels).  A reversed row is read forward from the
+//     mirrored column S - 4 - x (S % 4 == 0 keeps the 4-pixel groups aligned under the mirror) and reversed in registers.
+//   codes 4-7: a block turns the 32 x 32 pixel tile blockIdx.x = ty * ceil(S / 32) + tx through LDS, one dword (B | G << 8 | R << 16) per
+//     pixel at tile[i][j] (i = output x, j = output y inside the tile), row pitch TV_PITCH = 33 dwords.
+//       in:  thread (i = tid / 8, jg = tid % 8) reads source row r(xt + i), 4 pixels, and writes tile[i][4 jg + k], k = 0..3, as ds_write_b32:
+//            bank (33 i + 4 jg + k) % 32 = (i + 4 jg + k) % 32; a 32-lane half holds i = i0..i0+3, jg = 0..7 -> 32 distinct banks.
+//       out: thread (j = tid / 8, ig = tid % 8) reads tile[4 ig + k][j] as ds_read_b32: bank (33 (4 ig + k) + j) % 32 = (4 ig + k + j) % 32;
+//            a half holds j = j0..j0+3, ig = 0..7 -> 32 distinct banks.
+//     Conflict count by the (a / 4) % 32 rule per 32-lane half: 0 extra cycles on both sides (pitch 32 would put the column read of a
+//     half on 4 banks, 8-way).  Any pitch = 1 mod 8 does the same; 33 is the smallest above the tile.  (The compiler pairs the four
+//     accesses of a thread into two ds_write2_b32 / ds_read2_b32, which bank per dword by the same rule.)
+//     The grid has ceil(S / 32)^2 blocks per window, never fewer than the linear mapping needs; groups of 4 pixels past S (S % 32 != 0)
+//     are neither loaded nor stored, and S % 4 == 0 makes a group wholly inside or wholly outside.
+__global__ __launch_bounds__(256) void tile_cut_views_kernel(const uint8_t* __restrict__ pool, const int64_t* __restrict__ win, int S,
+                                                             float* __restrict__ dst)
+{
+    __shared__ uint32_t tile[TV_TILE * TV_PITCH];
+    const int w = blockIdx.y;
+    const int64_t* t = win + (int64_t)w * TV_ROW;
+    const uint8_t* src = pool + t[0];
+    const int H = (int)t[1], W = (int)t[2], x0 = (int)t[3], y0 = (int)t[4], code = (int)t[5];
+    const int64_t plane = (int64_t)S * S;
+    float* out = dst + (int64_t)w * 3 * plane;
+    if (code < 0 || code > 7) return;                                   // block-uniform: the slot stays untouched
+    if (code < 4) {
+        const int sq = S >> 2;
+        const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+        if (q >= (int64_t)S * sq) return;
+        const int y = (int)(q / sq);
+        const int x = (int)(q - (int64_t)y * sq) * 4;
+        const bool fx = code & 1, fy = code & 2;
+        uint32_t q12[3];
+        tv_load4(src, H, W, y0 + (fy ? S - 1 - y : y), x0 + (fx ? S - 4 - x : x), q12);
+        float* o = out + (int64_t)y * S + x;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {                                   // BGR -> RGB, .float() / 255 (ryolo_to_tensor's expression)
+            float v[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) v[k] = (float)TV_BYTE(q12, k * 3 + (2 - c)) / 255.0f;
+            *reinterpret_cast<float4*>(o + c * plane) = fx ? make_float4(v[3], v[2], v[1], v[0]) : make_float4(v[0], v[1], v[2], v[3]);
+        }
+        return;
+    }
+    const int nt = (S + TV_TILE - 1) / TV_TILE;
+    const int ty = blockIdx.x / nt, tx = blockIdx.x - ty * nt;          // blockIdx.x < nt * nt (the launch's grid)
+    const int xt = tx * TV_TILE, yt = ty * TV_TILE;                     // the tile's origin in the output
+    const bool fc = code == 5 || code == 7, fr = code == 6 || code == 7;
+    const int a = threadIdx.x >> 3, bg = (threadIdx.x & 7) * 4;
+    if (xt + a < S && yt + bg < S) {                                    // in: i = a, j = bg .. bg + 3
+        const int x = xt + a, y = yt + bg;
+        uint32_t q12[3];
+        tv_load4(src, H, W, y0 + (fr ? S - 1 - x : x), x0 + (fc ? S - 4 - y : y), q12);
+        uint32_t p[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) p[k] = TV_BYTE(q12, 3 * k) | TV_BYTE(q12, 3 * k + 1) << 8 | TV_BYTE(q12, 3 * k + 2) << 16;
+#pragma unroll
+        for (int k = 0; k < 4; k++) tile[a * TV_PITCH + bg + k] = fc ? p[3 - k] : p[k];     // a reversed row: reversed in registers
+    }
+    __syncthreads();
+    if (yt + a < S && xt + bg < S) {                                    // out: j = a, i = bg .. bg + 3
+        uint32_t p[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) p[k] = tile[(bg + k) * TV_PITCH + a];
+        float* o = out + (int64_t)(yt + a) * S + xt + bg;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            float v[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) v[k] = (float)((p[k] >> (8 * (2 - c))) & 255u) / 255.0f;
+            *reinterpret_cast<float4*>(o + c * plane) = make_float4(v[0], v[1], v[2], v[3]);
+        }
+    }
+}
+
+// tile_collect_kernel with the view's inverse map in front of the shift: geom rows (x0, y0, rate, view code), S the window size.  The
+// point map and the angle (fp32, one rounding per step; -theta is exact) follow include/ryolo.h; the six views that change theta wrap it
+// once through norm_angle's two selects (lib/general.py:14-15).  An entry with an unknown code is written as an empty slot.
+__global__ __launch_bounds__(256) void tile_collect_views_kernel(const float* __restrict__ dets, const int32_t* __restrict__ num, int64_t mk,
+                                                                 const float* __restrict__ geom, int64_t win0, int64_t nwin, int nc,
+                                                                 int64_t ld, float S, float* __restrict__ cand, float* __restrict__ key,
+                                                                 float* __restrict__ fkey)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = blockIdx.y;
+    if (j >= mk) return;
+    const int64_t wg = win0 + b;
+    const int64_t slot = wg * mk + j;
+    float* c = cand + slot * 7;
+    float s = -INFINITY;
+    int cls = -1;
+    const float* g = geom + wg * 4;
+    const int code = wg < nwin ? (int)g[3] : -1;
+    if (code >= 0 && code <= 7 && j < (int64_t)num[b]) {
+        const float* d = dets + ((int64_t)b * mk + j) * 7;
+        const float x0 = g[0], y0 = g[1], rate = g[2];
+        const float HALF_PI = 1.57079632679489661923f, PI = 3.14159265358979323846f;
+        const float vx = d[0], vy = d[1], th = d[4];
+        float px, py, t;
+        switch (code) {
+            case 0: px = vx; py = vy; t = th; break;
+            case 1: px = S - vx; py = vy; t = -th; break;
+            case 2: px = vx; py = S - vy; t = -th; break;
+            case 3: px = S - vx; py = S - vy; t = th; break;
+            case 4: px = vy; py = vx; t = HALF_PI - th; break;
+            case 5: px = S - vy; py = vx; t = th + HALF_PI; break;
+            case 6: px = vy; py = S - vx; t = th - HALF_PI; break;
+            default: px = S - vy; py = S - vx; t = HALF_PI - th; break;
+        }
+        if (code != 0 && code != 3) {
+            if (t >= HALF_PI) t = t - PI;
+            if (t < -HALF_PI) t = t + PI;
+        }
+        c[0] = (px + x0) / rate;
+        c[1] = (py + y0) / rate;
+        c[2] = d[2] / rate;
+        c[3] = d[3] / rate;
+        c[4] = t; c[5] = d[5]; c[6] = d[6];
+        s = d[5];
+        cls = (int)d[6];
+    } else {
+        for (int k = 0; k < 7; k++) c[k] = 0.f;
+    }
+    for (int k = 0; k < nc; k++) key[(int64_t)k * ld + slot] = k == cls ? s : -INFINITY;
+    fkey[slot] = -INFINITY;
+}
+
 extern "C" int ryolo_tile_cut(const uint8_t* pool, const int64_t* win, int64_t win0, int count, int S, float* dst, hipStream_t stream)
 {
     if (count < 0 || win0 < 0 || S <= 0) return RY_ERR_ARG;
@@ -153,6 +312,31 @@ extern "C" int ryolo_tile_collect(const float* dets, const int32_t* num, int bat
     if (!dets || !num || !geom || !cand || !fkey || (nc && !key)) return RY_ERR_ARG;
     hipLaunchKernelGGL(tile_collect_kernel, dim3((unsigned)ry_cdiv(mk, 256), batch), dim3(256), 0, stream, dets, num, mk, geom, win0, nwin, nc,
                        ld, cand, key, fkey);
+    RY_CHECK_LAUNCH();
+    return RY_OK;
+}
+
+extern "C" int ryolo_tile_cut_views(const uint8_t* pool, const int64_t* win, int64_t win0, int count, int S, float* dst, hipStream_t stream)
+{
+    if (count < 0 || win0 < 0 || S <= 0) return RY_ERR_ARG;
+    if (S % 4 != 0 || count > 65535) return RY_ERR_UNSUPPORTED;
+    if (count == 0) return RY_OK;
+    if (!pool || !win || !dst) return RY_ERR_ARG;
+    const int64_t nt = ry_cdiv((int64_t)S, TV_TILE);                    // nt * nt tiles >= ceil(S * S / 1024) blocks of the linear mapping
+    hipLaunchKernelGGL(tile_cut_views_kernel, dim3((unsigned)(nt * nt), count), dim3(256), 0, stream, pool, win + win0 * TV_ROW, S, dst);
+    RY_CHECK_LAUNCH();
+    return RY_OK;
+}
+
+extern "C" int ryolo_tile_collect_views(const float* dets, const int32_t* num, int batch, int64_t mk, const float* geom, int64_t win0,
+                                        int64_t nwin, int nc, int64_t ld, int S, float* cand, float* key, float* fkey, hipStream_t stream)
+{
+    if (batch < 0 || mk < 0 || win0 < 0 || nwin < 0 || nc < 0 || ld < 0 || S <= 0) return RY_ERR_ARG;
+    if ((win0 + batch) * mk > ld || batch > 65535) return RY_ERR_ARG;      // every slot of the group lies inside the candidate rows
+    if (batch == 0 || mk == 0) return RY_OK;
+    if (!dets || !num || !geom || !cand || !fkey || (nc && !key)) return RY_ERR_ARG;
+    hipLaunchKernelGGL(tile_collect_views_kernel, dim3((unsigned)ry_cdiv(mk, 256), batch), dim3(256), 0, stream, dets, num, mk, geom, win0,
+                       nwin, nc, ld, (float)S, cand, key, fkey);
     RY_CHECK_LAUNCH();
     return RY_OK;
 }

@@ -49,6 +49,8 @@ _SIGNATURES = {
     "ryolo_dets_to_polys": [_P, _P, _P, _I, _I, _L, _P, _P],
     "ryolo_tile_cut": [_P, _P, _L, _I, _I, _P, _P],
     "ryolo_tile_collect": [_P, _P, _I, _L, _P, _L, _L, _I, _L, _P, _P, _P, _P],
+    "ryolo_tile_cut_views": [_P, _P, _L, _I, _I, _P, _P],
+    "ryolo_tile_collect_views": [_P, _P, _I, _L, _P, _L, _L, _I, _L, _I, _P, _P, _P, _P],
     "ryolo_tile_merge_gather": [_P, _P, _P, _I, _L, _P, _P],
     "ryolo_tile_mark": [_P, _P, _P, _P, _I, _L, _L, _P, _P],
     "ryolo_tile_emit": [_P, _P, _P, _L, _P, _P],

@@ -4,7 +4,9 @@ forward, the decode and post_process), and the per-window detections are mapped 
 NMS — the workflow users of the reference rebuild by hand around detect.py, which only letterboxes a whole file to img_size.
 
     tile_plan(H, W, size, overlap, rates=(1.0,)) -> [(rate_index, x0, y0)]        the window table (host, pure Python)
+    tile_entries(H, W, size, overlap, rates, views) -> [(rate_index, x0, y0, view)]  windows x views, window-major
     TiledDetector(model, size, overlap, batch, ...)(scene) -> Tensor[n, 7]          (x, y, w, h, theta_rad, score, cls) in scene pixels
+    TiledDetector(..., views=("id", "hflip", "rot90"))                              every window also seen flipped / turned by 90 degrees (VIEWS)
     TiledDetector.run_async(scene) -> (out [max_det, 7], num [1] int32)             the same with the count left on the device
     TiledDetector.detect_files(paths) -> iterator of (path, Tensor[n, 7])           scene i + 1 decoded / uploaded while scene i runs
     write_dota_task1({name: dets}, out_dir, class_names)                            DOTA Task1 files (Task1_<class>.txt)
@@ -14,6 +16,13 @@ rows at the fixed slot window * mk + j, per-class keys); then per scene ryolo_to
 ryolo_nms_rotated_batched with batch = nc (no cls * 4096 offset: post_process's class separation collides on scenes wider than 4096 px),
 ryolo_tile_mark, ryolo_topk_desc over the kept entries (score desc, slot asc) and ryolo_tile_emit.  No allocation and no host read after the
 scene's upload; __call__ reads one count per scene.
+
+Views (test-time orientation ensembling; an overhead scene has no preferred orientation): with views other than ("id",) a scene's entries
+are windows x views, window-major (entry e = window_index * len(views) + view_index), so the views of one window are cut back to back.
+ryolo_tile_cut_views writes an entry's window in its view (flips by index arithmetic, the transposing views through LDS) and
+ryolo_tile_collect_views maps the view's boxes back to the window (point, theta wrapped into [-pi/2, pi/2)) in front of the shift; the
+candidate slot is e * mk + j and the merge is unchanged: it keeps the best-scoring box of a cluster (no score fusion across views).
+The definition of the eight views is in include/ryolo.h.
 """
 import math
 from collections import OrderedDict
@@ -26,6 +35,23 @@ from ..datasets import augment as A
 from . import general
 
 _SORT_MAX = 16384            # ryolo_topk_desc selects at most this many entries per row
+# the eight flip / 90-degree views of a window; a view's code in the device tables is its index here (include/ryolo.h)
+VIEWS = ("id", "hflip", "vflip", "rot180", "transpose", "rot90", "rot270", "antitranspose")
+
+
+def check_views(views):
+    """-> the tuple of view names, validated: known names, no duplicates, not empty."""
+    if isinstance(views, str):
+        raise ValueError(f"views must be a sequence of names from {VIEWS}, got the string {views!r}")
+    views = tuple(views)
+    if not views:
+        raise ValueError("views must name at least one view")
+    for v in views:
+        if v not in VIEWS:
+            raise ValueError(f"unknown view {v!r}: choose from {VIEWS}")
+    if len(set(views)) != len(views):
+        raise ValueError(f"views must not repeat, got {views}")
+    return views
 
 
 # ------------------------------------------------------------------------------------------ window plan
@@ -71,6 +97,13 @@ def tile_plan(H, W, size, overlap, rates=(1.0,)):
     return out
 
 
+def tile_entries(H, W, size, overlap, rates=(1.0,), views=("id",)):
+    """Entries of a scene: [(rate_index, x0, y0, view name)], every window of tile_plan once per view, window-major: entry
+    e = window_index * len(views) + view_index.  Detection j of entry e takes candidate slot e * mk + j."""
+    views = check_views(views)
+    return [(ri, x0, y0, v) for ri, x0, y0 in tile_plan(H, W, size, overlap, rates) for v in views]
+
+
 # ------------------------------------------------------------------------------------------ per-scene-shape buffers
 def _h2d(dst, arr):
     """Small host table -> existing device tensor through pinned memory, non-blocking on the current stream."""
@@ -80,26 +113,39 @@ def _h2d(dst, arr):
 
 
 class ScenePlan:
-    """Static buffers of one (H, W, rates): window table, candidate rows, class keys, merge and final-order buffers, resized copies.
-    `det` supplies device, batch, mk (detection rows per window), nc, size, overlap, rates, max_nms and max_det (a TiledDetector)."""
+    """Static buffers of one (H, W, rates, views): entry table, candidate rows, class keys, merge and final-order buffers, resized copies.
+    `det` supplies device, batch, mk (detection rows per window), nc, size, overlap, rates, max_nms and max_det (a TiledDetector) and
+    optionally views (default ("id",)).  An entry is a window seen through a view: entries = windows x views, window-major; T counts
+    entries, and groups of `batch` entries share one replay.  With views == ("id",) entries are the windows and the tables are those of
+    ryolo_tile_cut / ryolo_tile_collect; otherwise they carry the view code for ryolo_tile_cut_views / ryolo_tile_collect_views."""
 
     def __init__(self, det, H, W):
         dev, B, mk, nc, S = det.device, det.batch, det.mk, det.nc, det.size
         self.H, self.W = H, W
         self.batch, self.mk, self.nc, self.max_det = B, mk, nc, det.max_det
+        self.size = S
+        self.views = check_views(getattr(det, "views", ("id",)))
+        self.plain = self.views == ("id",)
         self.windows = tile_plan(H, W, S, det.overlap, det.rates)
+        self.entries = tile_entries(H, W, S, det.overlap, det.rates, self.views)
         self.extents = [resized_extent(H, W, r) for r in det.rates]
-        T = self.T = len(self.windows)
+        T = self.T = len(self.entries)
         self.groups = (T + B - 1) // B
         ld = self.ld = self.groups * B * mk
         f32, i32, i64 = torch.float32, torch.int32, torch.int64
-        wa = np.asarray(self.windows, dtype=np.int64).reshape(-1, 3)
+        wa = np.asarray([e[:3] for e in self.entries], dtype=np.int64).reshape(-1, 3)
+        code = np.asarray([VIEWS.index(e[3]) for e in self.entries], dtype=np.int64)
         ext = np.asarray(self.extents, dtype=np.int64)
-        self.rows = np.stack([np.zeros(T, np.int64), ext[wa[:, 0], 0], ext[wa[:, 0], 1], wa[:, 1], wa[:, 2]], 1)   # src_off set per scene
+        cols = [np.zeros(T, np.int64), ext[wa[:, 0], 0], ext[wa[:, 0], 1], wa[:, 1], wa[:, 2]]       # src_off set per scene
+        gcols = [wa[:, 1], wa[:, 2], np.asarray(det.rates, np.float32)[wa[:, 0]]]
+        if not self.plain:
+            cols.append(code)
+            gcols.append(code)
+        self.rows = np.stack(cols, 1)
         self.rate_of = wa[:, 0]
-        self.win = torch.empty((T, 5), dtype=i64, device=dev)
-        self.geom = torch.empty((T, 3), dtype=f32, device=dev)
-        _h2d(self.geom, np.stack([wa[:, 1], wa[:, 2], np.asarray(det.rates, np.float32)[wa[:, 0]]], 1).astype(np.float32))
+        self.win = torch.empty(self.rows.shape, dtype=i64, device=dev)
+        self.geom = torch.empty((T, len(gcols)), dtype=f32, device=dev)
+        _h2d(self.geom, np.stack(gcols, 1).astype(np.float32))
         # resized copies of the scene (rates != 1), one staging buffer
         self.stage_off, total = [], 0
         for r, (h, w) in zip(det.rates, self.extents):
@@ -108,7 +154,7 @@ class ScenePlan:
                 total += ((h * w * 3 + 15) // 16) * 16
         self.stage = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
         self.resize_items = [(ri, h, w) for ri, (r, (h, w)) in enumerate(zip(det.rates, self.extents)) if r != 1.0]
-        # candidates and keys: every slot is written by ryolo_tile_collect
+        # candidates and keys: every slot is written by ryolo_tile_collect / ryolo_tile_collect_views
         self.cand = torch.empty((ld, 7), dtype=f32, device=dev)
         self.key = torch.empty((nc, ld), dtype=f32, device=dev)
         self.fkey = torch.empty(ld, dtype=f32, device=dev)
@@ -130,11 +176,21 @@ class ScenePlan:
         self.num = torch.empty(1, dtype=i32, device=dev)
         self.out = torch.empty((self.max_det, 7), dtype=f32, device=dev)
 
+    def cut(self, scene, g, dst):
+        """Group g's entries of the scene at device address `scene` -> dst [batch, 3, size, size] (slots past the last entry untouched)."""
+        e0 = g * self.batch
+        hip.call("ryolo_tile_cut" if self.plain else "ryolo_tile_cut_views", scene, hip.ptr(self.win), e0, min(self.batch, self.T - e0),
+                 self.size, hip.ptr(dst), hip.stream())
+
     def collect(self, dets, num, g):
         """Group g's post_process output dets [batch, mk, 7] / num [batch] -> candidate rows and class keys of its slots."""
         B = self.batch
-        hip.call("ryolo_tile_collect", hip.ptr(dets), hip.ptr(num), B, self.mk, hip.ptr(self.geom), g * B, self.T, self.nc, self.ld,
-                 hip.ptr(self.cand), hip.ptr(self.key), hip.ptr(self.fkey), hip.stream())
+        if self.plain:
+            hip.call("ryolo_tile_collect", hip.ptr(dets), hip.ptr(num), B, self.mk, hip.ptr(self.geom), g * B, self.T, self.nc, self.ld,
+                     hip.ptr(self.cand), hip.ptr(self.key), hip.ptr(self.fkey), hip.stream())
+        else:
+            hip.call("ryolo_tile_collect_views", hip.ptr(dets), hip.ptr(num), B, self.mk, hip.ptr(self.geom), g * B, self.T, self.nc,
+                     self.ld, self.size, hip.ptr(self.cand), hip.ptr(self.key), hip.ptr(self.fkey), hip.stream())
 
     def merge(self, merge_iou, gt_only=True):
         """Class-wise rotated NMS over every collected candidate, then the final order -> (out [max_det, 7], num [1]) on the device."""
@@ -169,11 +225,13 @@ class TiledDetector:
     conf_thres / iou_thres: post_process of every window (captured with the graph).  merge_iou (default iou_thres) and gt_only: the
     class-wise rotated NMS of the merge.  rates: the scene is resized once per rate (INTER_AREA below 1, INTER_LINEAR above; rate 1 is cut
     straight from the scene) and every resized copy is tiled; boxes are mapped back to the original scene.  max_nms: candidates per class
-    entering the merge; max_det: detections per scene."""
+    entering the merge; max_det: detections per scene.  views: names from VIEWS, in the order their entries take inside a window; every
+    window runs once per view and all views' boxes enter the one merge, which keeps the best-scoring box of a cluster."""
 
     def __init__(self, model, size=1024, overlap=200, batch=8, conf_thres=0.1, iou_thres=0.4, merge_iou=None, rates=(1.0,), max_nms=5000,
-                 max_det=5000, gt_only=True):
+                 max_det=5000, gt_only=True, views=("id",)):
         rates = tuple(float(r) for r in rates)
+        views = check_views(views)
         tile_plan(size, size, size, overlap, rates)                      # argument validation
         if int(batch) < 1:
             raise ValueError(f"TiledDetector: batch must be >= 1, got {batch}")
@@ -182,7 +240,7 @@ class TiledDetector:
                 raise ValueError(f"TiledDetector: {name} must lie in [1, {_SORT_MAX}], got {v}")
         if model.training:
             raise RuntimeError("TiledDetector: call model.eval() first")
-        self.size, self.overlap, self.batch, self.rates = int(size), int(overlap), int(batch), rates
+        self.size, self.overlap, self.batch, self.rates, self.views = int(size), int(overlap), int(batch), rates, views
         self.conf_thres, self.iou_thres = float(conf_thres), float(iou_thres)
         self.merge_iou = self.iou_thres if merge_iou is None else float(merge_iou)
         self.max_nms, self.max_det, self.gt_only = int(max_nms), int(max_det), bool(gt_only)
@@ -191,13 +249,13 @@ class TiledDetector:
         self.run = model.capture_inference(self.batch, self.size, post=(self.conf_thres, self.iou_thres))
         self.device = self.run.static_input.device
         self.nc, self.mk = self.run.post_plan.nc, self.run.post_plan.mk
-        self._plans = OrderedDict()          # (H, W, rates) -> ScenePlan, least recently used first
+        self._plans = OrderedDict()          # (H, W, rates, views) -> ScenePlan, least recently used first
         self._plans_max = 4
         self._side = None
 
     # ---- buffers
     def plan(self, H, W):
-        key = (int(H), int(W), self.rates)
+        key = (int(H), int(W), self.rates, tuple(self.views))
         p = self._plans.pop(key, None)
         if p is None:
             while len(self._plans) >= self._plans_max:
@@ -241,10 +299,9 @@ class TiledDetector:
         rows = p.rows.copy()
         rows[:, 0] = np.asarray(src, dtype=np.int64)[p.rate_of]
         _h2d(p.win, rows)
-        run, B = self.run, self.batch
+        run = self.run
         for g in range(p.groups):
-            w0 = g * B
-            hip.call("ryolo_tile_cut", scene, hip.ptr(p.win), w0, min(B, p.T - w0), self.size, hip.ptr(run.static_input), st)
+            p.cut(scene, g, run.static_input)
             run.graph.replay()
             p.collect(run.post_plan.out, run.post_plan.num, g)
         return p.merge(self.merge_iou, self.gt_only)
@@ -260,7 +317,7 @@ class TiledDetector:
 
     def __call__(self, scene):
         """HxWx3 uint8 BGR numpy array (cv2.imread) or device tensor -> Tensor[n, 7] (x, y, w, h, theta_rad, score, cls) in scene pixels,
-        score descending (ties: window order, then the window's own order)."""
+        score descending (ties: window order, then the order of `views`, then the entry's own order)."""
         out, num = self.run_async(scene)
         n = int(num.item())                  # the one device -> host read of the scene
         return out[:n].clone()

@@ -1,12 +1,15 @@
 """Full-scene (tiled) detection throughput: yolov7 kfiou nc=16 (synth.fill_state weights), a synthetic 4000 x 4000 scene, S=1024,
-overlap=200, batch=8 (25 windows in 4 groups).  Prints one JSON line:
+overlap=200, batch=8 (25 windows in 4 groups; with VIEWS every window once per view: entries = windows x views in groups of 8).  Prints
+one JSON line:
   scene_ms / windows_per_s        TiledDetector.run_async + the count read, per scene
+  entries / entry_ms              windows x views, and scene_ms per entry
   replay_ms                       the same number of bare captured-graph replays (forward + post_process in the graph)
   glue_ms / glue_share            scene_ms - replay_ms: cut, collect, merge, final order, launches (target <= 5 % of scene time)
   naive_ms                        the Python loop a user writes today: per-window device slicing + to-tensor, the captured forward without
                                   post, post_process per group, a host-side shift, per-class nms_rotated
   files_overlap_ms / files_serial_ms   detect_files over 8 scenes with / without the side-stream upload overlap (decode = an in-memory copy)
-Environment: SCENE (4000), S (1024), OVERLAP (200), B (8), CONF (0.1), N (iterations, 10)."""
+The naive loop has no views: naive_ms and speedup_vs_naive compare like with like only for VIEWS=id.
+Environment: SCENE (4000), S (1024), OVERLAP (200), B (8), CONF (0.1), N (iterations, 10), VIEWS (comma list of lib.tiled.VIEWS names, id)."""
 import json
 import os
 import sys
@@ -17,22 +20,25 @@ import numpy as np
 import torch
 
 from ryolov4_amd.lib import general
-from ryolov4_amd.lib.tiled import TiledDetector, tile_plan
+from ryolov4_amd.lib.tiled import TiledDetector, tile_entries, tile_plan
 from ryolov4_amd.model.yolo import Yolo
 from ryolov4_amd.synth import CFG, fill_state
 
 dev = torch.device("cuda:0")
 SC, S, OV, B = int(os.environ.get("SCENE", 4000)), int(os.environ.get("S", 1024)), int(os.environ.get("OVERLAP", 200)), int(os.environ.get("B", 8))
 CONF, IOU, N = float(os.environ.get("CONF", 0.1)), 0.4, int(os.environ.get("N", 10))
+VIEWS = tuple(v.strip() for v in os.environ.get("VIEWS", "id").split(",") if v.strip())
 
 net = Yolo(16, CFG, "kfiou", "yolov7")
 net.load_state_dict(fill_state(net.state_dict()))
 net.to(dev).eval()
-det = TiledDetector(net, size=S, overlap=OV, batch=B, conf_thres=CONF, iou_thres=IOU)
+det = TiledDetector(net, size=S, overlap=OV, batch=B, conf_thres=CONF, iou_thres=IOU, views=VIEWS)
 scene = np.random.RandomState(0).randint(0, 256, (SC, SC, 3)).astype(np.uint8)
 scene_dev = torch.from_numpy(scene).to(dev)
 wins = tile_plan(SC, SC, S, OV)
-groups = -(-len(wins) // B)
+entries = len(tile_entries(SC, SC, S, OV, views=VIEWS))
+groups = -(-len(wins) // B)                                     # of the naive loop (windows only)
+egroups = -(-entries // B)                                      # replays per scene
 
 
 def wall(fn, n=N):
@@ -52,7 +58,7 @@ def tiled():
 
 
 def replays():
-    for _ in range(groups):
+    for _ in range(egroups):
         det.run.graph.replay()
     torch.cuda.synchronize()
 
@@ -104,8 +110,9 @@ t_naive = wall(naive, max(2, N // 3))
 t_fo = wall(lambda: run_files(True), 2) / len(files)
 t_fs = wall(lambda: run_files(False), 2) / len(files)
 n_tiled, n_naive = tiled(), naive()
-print(json.dumps({"scene": SC, "S": S, "overlap": OV, "batch": B, "windows": len(wins), "groups": groups, "padded_slots": groups * B - len(wins),
+print(json.dumps({"scene": SC, "S": S, "overlap": OV, "batch": B, "views": list(VIEWS), "windows": len(wins), "entries": entries, "groups": egroups,
+                  "padded_slots": egroups * B - entries,
                   "conf_thres": CONF, "detections": n_tiled, "naive_detections": n_naive,
-                  "scene_ms": round(t_scene, 3), "windows_per_s": round(len(wins) / t_scene * 1e3, 1), "replay_ms": round(t_rep, 3),
+                  "scene_ms": round(t_scene, 3), "entry_ms": round(t_scene / entries, 3), "windows_per_s": round(len(wins) / t_scene * 1e3, 1), "replay_ms": round(t_rep, 3),
                   "glue_ms": round(t_scene - t_rep, 3), "glue_share": round((t_scene - t_rep) / t_scene, 4), "naive_ms": round(t_naive, 3),
                   "speedup_vs_naive": round(t_naive / t_scene, 2), "files_overlap_ms": round(t_fo, 3), "files_serial_ms": round(t_fs, 3)}))
