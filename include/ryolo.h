@@ -44,6 +44,18 @@ int ryolo_nms_rotated_batched(const float* boxes, const int32_t* counts, int bat
                               int gt_only, int64_t max_keep, void* workspace, size_t workspace_bytes, int64_t* keep,
                               int64_t keep_stride, int32_t* num_keep, ryolo_stream_t stream);
 
+/* Cluster owners of the NMS that has just run: owner [batch, nmax] int32, per row b and sorted position p
+ *   p >= counts[b]                     -1
+ *   p kept                             p
+ *   otherwise                          the smallest kept k < p whose suppression bit (k, p) is set (IoU > thr with gt_only, >= thr without:
+ *                                      the very decision the NMS took; such a k exists by the greedy construction)
+ * The bits are read from the mask ryolo_nms_rotated_batched left in its workspace ([batch][nmax][ceil(nmax / 64)] u64, upper triangle), so
+ * the contract is: same workspace, same stream, same batch / nmax / counts, directly after that call, with its keep / keep_stride /
+ * num_keep, and the NMS not cut short (max_keep <= 0 or >= nmax, keep_stride >= the number kept): a position left undecided by a capped
+ * NMS gets -1.  No IoU is evaluated again. */
+int ryolo_nms_owner(const int32_t* counts, int batch, int64_t nmax, const void* workspace, size_t workspace_bytes, const int64_t* keep,
+                    int64_t keep_stride, const int32_t* num_keep, int32_t* owner, ryolo_stream_t stream);
+
 /* IoU[n, m] row-major = pairwise_iou_rotated(b1[n,5], b2[m,5]) (test.py:135).
  * workspace >= align256(n*48) + m*48 bytes. */
 int ryolo_box_iou_rotated(const float* b1, int n, const float* b2, int m, void* workspace, size_t workspace_bytes,
@@ -377,6 +389,36 @@ int ryolo_tile_merge_gather(const float* cand, const float* skey, const int64_t*
 /* kept positions keep [nc, keep_stride] / num_keep [nc] of that NMS -> fkey[order[c, keep[c, j]]] = skey[c, keep[c, j]] */
 int ryolo_tile_mark(const float* skey, const int64_t* order, const int64_t* keep, const int32_t* num_keep, int nc, int64_t K,
                     int64_t keep_stride, float* fkey, ryolo_stream_t stream);
+/* Cluster fusion (lib/tiled.py fuse = "box" | "wbf"): in place of ryolo_tile_mark, after ryolo_nms_owner.  Per class c, positions
+ * p = 0 .. nsel[c] - 1 are in (score desc, slot asc) order, rows r_p = cand[order[c, p]] = (x, y, w, h, theta rad, s, cls), K the keep set
+ * of the NMS and owner [nc, K] int32 its clusters: every selected candidate belongs to the cluster of exactly one kept box; candidates
+ * not selected (beyond K per class) belong to none.  Cluster k, members in ascending position, the owner first; fp32, one operation
+ * per arrow, no FMA contraction, constants (float)pi, (float)pi/2, (float)pi/4:
+ *   m = 1; W = s_k; ax = 0; ay = 0; aw = s_k*w_k; ah = s_k*h_k; ad = 0
+ *   for each further member i, ascending position:
+ *       d = theta_i - theta_k;  if d >= pi/2: d = d - pi;   if d < -pi/2: d = d + pi          (both tests, in this order)
+ *       (wi, hi) = (w_i, h_i)
+ *       if d > pi/4: swap wi, hi; d = d - pi/2     else if d < -pi/4: swap wi, hi; d = d + pi/2
+ *       W = W + s_i;  ax = ax + s_i*(x_i - x_k);  ay = ay + s_i*(y_i - y_k)
+ *       aw = aw + s_i*wi;  ah = ah + s_i*hi;  ad = ad + s_i*d;  m = m + 1
+ *   x = x_k + ax/W;  y = y_k + ay/W;  w = aw/W;  h = ah/W
+ *   theta = theta_k + ad/W;  if theta >= pi/2: theta = theta - pi;  if theta < -pi/2: theta = theta + pi
+ * (theta has period pi, and (w, h, theta) and (h, w, theta +- pi/2) are the same box: near-square objects come back both ways from the
+ * transposing views.)  A cluster with m == 1 emits its row bit for bit, theta unwrapped as the plain collect pass leaves it.  The class
+ * column is the owner's; the fused box stays in the owner's frame (no canonical w / h swap afterwards).
+ * Score, mode 0 ("box"): the owner's score, bits unchanged.  Mode 1 ("wbf"): (W / (float)m) * ((float)min(m, n_ens) / (float)n_ens) with
+ * n_ens = rates x views of the scene: the mean member score, scaled down when fewer boxes than ensemble members support it (also for
+ * m == 1, whose geometry is still copied).
+ * Writes fused [ld][7] and fkey [ld] at the owner's slot order[c, k] only, each once; cand is not modified (fused != cand); no atomics,
+ * deterministic.  The final order is then ryolo_topk_desc of fkey (fused score desc, owner's slot asc) and ryolo_tile_emit with fused as
+ * its cand argument.  keep_stride <= K.
+ * Precondition: keep, order and nsel are the NMS's and ryolo_topk_desc's own outputs, so every kept position is < min(nsel[c], K) and
+ * every slot order[c, p] of a selected position is in [0, ld).  The arrays live on the device and the call does not read them back: a kept
+ * box whose position or slot is outside these ranges writes nothing (its slot of fused and fkey keeps what it held), and a member whose
+ * slot is outside [0, ld) is counted in m but adds zero to every sum.  No access leaves the buffers either way. */
+int ryolo_tile_fuse(const float* cand, const int64_t* order, const int32_t* nsel, const int64_t* keep, const int32_t* num_keep,
+                    const int32_t* owner, int nc, int64_t K, int64_t keep_stride, int64_t ld, int mode, int n_ens, float* fused, float* fkey,
+                    ryolo_stream_t stream);
 /* order [>= num[0]] = ryolo_topk_desc of fkey, num [1] its selection count -> out [max_det, 7] = cand[order[j]] for j < num[0], zeros after */
 int ryolo_tile_emit(const float* cand, const int64_t* order, const int32_t* num, int64_t max_det, float* out, ryolo_stream_t stream);
 

@@ -15,6 +15,7 @@
 //                           word with ballot/readlane (loop length = number of rows that suppress anything, not 64),
 //                           then all 16 waves OR the kept rows into an LDS-resident `removed` bitmap;
 //                           stops as soon as max_keep boxes are kept (post_process keeps only max_det=1500).
+//   4. nms_owner_kernel   (optional, ryolo_nms_owner) which kept box removed each suppressed one, read back from the same mask.
 #include "common.h"
 #include "rotated_iou.h"
 
@@ -202,6 +203,64 @@ __global__ __launch_bounds__(1024) void nms_reduce_kernel(const unsigned long lo
     }
 }
 
+// Cluster owners from the suppression mask the NMS has just left in its workspace (ryolo_nms_owner): owner[p] = p for a kept position,
+// otherwise the smallest kept k < p whose bit (k, p) is set — the row that removed p first in the greedy pass.  No second IoU: the
+// decision is the mask's.  One wave = the 64 positions of mask word wp; it walks the ascending keep list 64 kept rows at a time (lane l
+// loads word wp of kept row keep[j0 + l]; rows at or past (wp + 1) * 64 end the walk: the list is ascending and their words of column wp
+// were never written), and turns the 64 x 64 bit block with one ballot per still-open column that has a bit in the batch (wave OR).
+// A kept position has no bit in any kept row, so it never enters that loop; it is marked through the keep list itself.
+__device__ __forceinline__ unsigned long long wave_or64(unsigned long long v)
+{
+    unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+        lo |= (unsigned)__shfl_xor((int)lo, o);
+        hi |= (unsigned)__shfl_xor((int)hi, o);
+    }
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+__global__ __launch_bounds__(256) void nms_owner_kernel(const unsigned long long* __restrict__ mask, const int32_t* __restrict__ counts,
+                                                        int64_t nmax, int nw, const int64_t* __restrict__ keep, int64_t keep_stride,
+                                                        const int32_t* __restrict__ num_keep, int32_t* __restrict__ owner)
+{
+    __shared__ unsigned long long keptw[4];
+    const int img = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t wp = (int64_t)blockIdx.x * 4 + wave;
+    int64_t n = nmax;
+    if (counts) { n = counts[img]; if (n > nmax) n = nmax; if (n < 0) n = 0; }
+    int64_t nk = num_keep[img];
+    if (nk > keep_stride) nk = keep_stride;
+    if (lane == 0) keptw[wave] = 0ull;
+    __syncthreads();
+    const int64_t p = wp * TILE + lane;
+    const int64_t lim = min(n, (wp + 1) * TILE);                // kept rows below `lim` can own a position of this word
+    int own = -1;
+    if (wp < nw && wp * TILE < n) {                             // wave-uniform
+        for (int64_t j0 = 0; j0 < nk; j0 += 64) {
+            const int64_t kidx = j0 + lane < nk ? keep[(int64_t)img * keep_stride + j0 + lane] : -1;
+            const bool valid = kidx >= 0 && kidx < lim;
+            unsigned long long w = valid ? mask[((int64_t)img * nmax + kidx) * nw + wp] : 0ull;
+            if (valid && (kidx >> 6) == wp)                     // a kept row of this word's own tile: mark it (nms_mask_kernel left
+                atomicOr(&keptw[wave], 1ull << (kidx & 63));    // only its bits c > r in the diagonal word)
+            unsigned long long need = __ballot(own < 0) & wave_or64(w);
+            while (need) {
+                const int b = __builtin_ctzll(need);
+                need &= need - 1;
+                const unsigned long long m = __ballot((w >> b) & 1ull);          // kept rows of the batch that suppress column b: m != 0
+                const int kk = __builtin_amdgcn_readlane((int)kidx, __builtin_ctzll(m));
+                if (lane == b) own = kk;
+            }
+            if (__ballot(valid) != ~0ull) break;                // the list ended or passed `lim`
+        }
+    }
+    __syncthreads();
+    if (wp < nw && p < nmax) {
+        const bool kept = (keptw[wave] >> lane) & 1ull;
+        owner[(int64_t)img * nmax + p] = p < n ? (kept ? (int32_t)p : own) : -1;
+    }
+}
+
 // IoU[N,M] (row-major) — test.py:135 of the reference (mAP matching).  64x64 tiles, same prune-then-compute idea.
 __global__ __launch_bounds__(256) void pairwise_iou_kernel(const BoxPrep* __restrict__ p1, int n, const BoxPrep* __restrict__ p2, int m,
                                                            float* __restrict__ out)
@@ -273,6 +332,25 @@ extern "C" int ryolo_nms_rotated_batched(const float* boxes, const int32_t* coun
     const size_t lds = (size_t)(nw + 2) * 8;
     hipLaunchKernelGGL(nms_reduce_kernel, dim3(batch), dim3(1024), lds, stream, mask, counts, nmax, nw, max_keep, keep,
                        keep_stride, num_keep);
+    RY_CHECK_LAUNCH();
+    return RY_OK;
+}
+
+extern "C" int ryolo_nms_owner(const int32_t* counts, int batch, int64_t nmax, const void* ws, size_t ws_bytes, const int64_t* keep,
+                               int64_t keep_stride, const int32_t* num_keep, int32_t* owner, hipStream_t stream)
+{
+    if (batch < 0 || nmax < 0 || keep_stride < 0 || batch > 65535) return RY_ERR_ARG;
+    if (batch == 0 || nmax == 0) return RY_OK;
+    if (!ws || !keep || !num_keep || !owner || keep_stride == 0) return RY_ERR_ARG;
+    if (nmax > 65536 * 8) return RY_ERR_UNSUPPORTED;
+    size_t need;
+    ryolo_nms_workspace_bytes(batch, nmax, &need);
+    if (ws_bytes < need) return RY_ERR_WORKSPACE;
+    const int nw = (int)ry_cdiv(nmax, TILE);
+    const unsigned long long* mask = reinterpret_cast<const unsigned long long*>(
+        reinterpret_cast<const char*>(ws) + align256((size_t)batch * nmax * sizeof(BoxPrep)));
+    hipLaunchKernelGGL(nms_owner_kernel, dim3((unsigned)ry_cdiv(nw, 4), batch), dim3(256), 0, stream, mask, counts, nmax, nw, keep,
+                       keep_stride, num_keep, owner);
     RY_CHECK_LAUNCH();
     return RY_OK;
 }

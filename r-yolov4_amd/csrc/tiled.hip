@@ -16,8 +16,10 @@
 //                        separates classes by cls * 4096 px (lib/general.py:14), which collides on scenes wider than 4096 px; here a
 //                        class is its own NMS batch row (ryolo_nms_rotated_batched with batch = nc).
 //   tile_mark_kernel     kept entries -> final key [ld] by slot (the collect pass reset it to -inf)
+//   tile_fuse_kernel     (fused merge, in place of tile_mark_kernel, after ryolo_nms_owner) a kept box absorbs the boxes it suppressed:
+//                        score-weighted rotated box into fused [ld][7] and the fused score into the final key, both at the owner's slot
 //   (ryolo_topk_desc over the final key: score desc, slot asc, capped at max_det)
-//   tile_emit_kernel     out [max_det,7] = candidate rows in that order, zero padded.
+//   tile_emit_kernel     out [max_det,7] = candidate (or fused) rows in that order, zero padded.
 // Compiled with -ffp-contract=off: the coordinate mapping (x + x0) / rate is restated bit for bit by numpy in the tests.
 #include "common.h"
 
@@ -119,6 +121,102 @@ __global__ __launch_bounds__(256) void tile_mark_kernel(const float* __restrict_
     if (j >= keep_stride || j >= (int64_t)num_keep[c]) return;
     const int64_t e = (int64_t)c * K + keep[(int64_t)c * keep_stride + j];
     fkey[order[e]] = skey[e];                                          // a slot belongs to one class row: no two threads share it
+}
+
+// Cluster fusion (include/ryolo.h states the arithmetic): one wave = one kept box k of class blockIdx.y.  The wave reads the class's
+// owner row from position k + 1 to the end of the selection, 256 positions per step (four coalesced dword loads per lane in flight),
+// and takes one ballot per 64: the set bits are the cluster's members in ascending position.  A member's lane loads its candidate row
+// and computes everything that depends on the member and the owner only (the wrapped angle difference, the w / h swap, the five
+// products with its score); the six running sums are then advanced member by member in bit order on wave-uniform values (readlane), so
+// the order of the additions is the defined one whatever the cluster's size.  Lane 0 writes the fused row and the fused score at the
+// owner's slot: every output once, no atomics, cand is only read.
+__device__ __forceinline__ float tf_lane(float v, int l)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
+}
+
+__global__ __launch_bounds__(256) void tile_fuse_kernel(const float* __restrict__ cand, const int64_t* __restrict__ order,
+                                                        const int32_t* __restrict__ nsel, const int64_t* __restrict__ keep,
+                                                        const int32_t* __restrict__ num_keep, const int32_t* __restrict__ owner, int64_t K,
+                                                        int64_t keep_stride, int64_t ld, int wbf, int n_ens, float* __restrict__ fused,
+                                                        float* __restrict__ fkey)
+{
+    const float PI = 3.14159265358979323846f, HALF_PI = 1.57079632679489661923f, QUARTER_PI = 0.78539816339744830962f;
+    const int c = blockIdx.y, lane = threadIdx.x & 63;
+    const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    int64_t nk = num_keep[c];
+    if (nk > keep_stride) nk = keep_stride;
+    if (j >= nk) return;                                                // wave-uniform, like every exit below
+    int64_t n = nsel[c];
+    if (n > K) n = K;
+    const int64_t k = keep[(int64_t)c * keep_stride + j];
+    if (k < 0 || k >= n) return;
+    const int64_t* ord = order + (int64_t)c * K;
+    const int32_t* own = owner + (int64_t)c * K;
+    const int64_t slot = ord[k];
+    if (slot < 0 || slot >= ld) return;
+    const float* rk = cand + slot * 7;
+    const float xk = rk[0], yk = rk[1], wk = rk[2], hk = rk[3], tk = rk[4], sk = rk[5];
+    float W = sk, ax = 0.f, ay = 0.f, aw = sk * wk, ah = sk * hk, ad = 0.f;
+    int m = 1;
+    for (int64_t base = k + 1; base < n; base += 256) {
+        int32_t o[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int64_t p = base + 64 * u + lane;
+            o[u] = p < n ? own[p] : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const bool hit = o[u] == (int32_t)k;
+            unsigned long long mm = __ballot(hit);
+            if (!mm) continue;
+            float ts = 0.f, tx = 0.f, ty = 0.f, tw = 0.f, th = 0.f, td = 0.f;
+            if (hit) {
+                const int64_t si = ord[base + 64 * u + lane];
+                if (si >= 0 && si < ld) {
+                    const float* r = cand + si * 7;
+                    float d = r[4] - tk;
+                    if (d >= HALF_PI) d = d - PI;
+                    if (d < -HALF_PI) d = d + PI;
+                    float wi = r[2], hi = r[3];
+                    if (d > QUARTER_PI) { const float t = wi; wi = hi; hi = t; d = d - HALF_PI; }
+                    else if (d < -QUARTER_PI) { const float t = wi; wi = hi; hi = t; d = d + HALF_PI; }
+                    ts = r[5];
+                    tx = ts * (r[0] - xk);
+                    ty = ts * (r[1] - yk);
+                    tw = ts * wi;
+                    th = ts * hi;
+                    td = ts * d;
+                }
+            }
+            while (mm) {
+                const int l = __builtin_ctzll(mm);
+                mm &= mm - 1;
+                W = W + tf_lane(ts, l);
+                ax = ax + tf_lane(tx, l);
+                ay = ay + tf_lane(ty, l);
+                aw = aw + tf_lane(tw, l);
+                ah = ah + tf_lane(th, l);
+                ad = ad + tf_lane(td, l);
+                m++;
+            }
+        }
+    }
+    if (lane != 0) return;
+    float* o7 = fused + slot * 7;
+    if (m == 1) {
+        o7[0] = xk; o7[1] = yk; o7[2] = wk; o7[3] = hk; o7[4] = tk;     // a lone box: its row on the bits, theta unwrapped
+    } else {
+        float t = tk + ad / W;
+        if (t >= HALF_PI) t = t - PI;
+        if (t < -HALF_PI) t = t + PI;
+        o7[0] = xk + ax / W; o7[1] = yk + ay / W; o7[2] = aw / W; o7[3] = ah / W; o7[4] = t;
+    }
+    const float s = wbf ? (W / (float)m) * ((float)(m < n_ens ? m : n_ens) / (float)n_ens) : sk;
+    o7[5] = s;
+    o7[6] = rk[6];
+    fkey[slot] = s;
 }
 
 __global__ __launch_bounds__(256) void tile_emit_kernel(const float* __restrict__ cand, const int64_t* __restrict__ order,
@@ -360,6 +458,20 @@ extern "C" int ryolo_tile_mark(const float* skey, const int64_t* order, const in
     if (!skey || !order || !keep || !num_keep || !fkey) return RY_ERR_ARG;
     hipLaunchKernelGGL(tile_mark_kernel, dim3((unsigned)ry_cdiv(keep_stride, 256), nc), dim3(256), 0, stream, skey, order, keep, num_keep, K,
                        keep_stride, fkey);
+    RY_CHECK_LAUNCH();
+    return RY_OK;
+}
+
+extern "C" int ryolo_tile_fuse(const float* cand, const int64_t* order, const int32_t* nsel, const int64_t* keep, const int32_t* num_keep,
+                               const int32_t* owner, int nc, int64_t K, int64_t keep_stride, int64_t ld, int mode, int n_ens, float* fused,
+                               float* fkey, hipStream_t stream)
+{
+    if (nc < 0 || K < 0 || keep_stride < 0 || keep_stride > K || ld < 0 || nc > 65535) return RY_ERR_ARG;
+    if ((mode != 0 && mode != 1) || n_ens < 1) return RY_ERR_ARG;
+    if (nc == 0 || keep_stride == 0) return RY_OK;
+    if (!cand || !order || !nsel || !keep || !num_keep || !owner || !fused || !fkey || fused == cand) return RY_ERR_ARG;
+    hipLaunchKernelGGL(tile_fuse_kernel, dim3((unsigned)ry_cdiv(keep_stride, 4), nc), dim3(256), 0, stream, cand, order, nsel, keep, num_keep,
+                       owner, K, keep_stride, ld, mode, n_ens, fused, fkey);
     RY_CHECK_LAUNCH();
     return RY_OK;
 }

@@ -54,6 +54,8 @@ _SIGNATURES = {
     "ryolo_tile_merge_gather": [_P, _P, _P, _I, _L, _P, _P],
     "ryolo_tile_mark": [_P, _P, _P, _P, _I, _L, _L, _P, _P],
     "ryolo_tile_emit": [_P, _P, _P, _L, _P, _P],
+    "ryolo_nms_owner": [_P, _I, _L, _P, _Z, _P, _L, _P, _P, _P],
+    "ryolo_tile_fuse": [_P, _P, _P, _P, _P, _P, _I, _L, _L, _L, _I, _I, _P, _P, _P],
 }
 _lib = None
 

@@ -7,6 +7,7 @@ NMS — the workflow users of the reference rebuild by hand around detect.py, wh
     tile_entries(H, W, size, overlap, rates, views) -> [(rate_index, x0, y0, view)]  windows x views, window-major
     TiledDetector(model, size, overlap, batch, ...)(scene) -> Tensor[n, 7]          (x, y, w, h, theta_rad, score, cls) in scene pixels
     TiledDetector(..., views=("id", "hflip", "rot90"))                              every window also seen flipped / turned by 90 degrees (VIEWS)
+    TiledDetector(..., fuse="box" | "wbf")                                          kept boxes absorb the boxes they suppressed (FUSE)
     TiledDetector.run_async(scene) -> (out [max_det, 7], num [1] int32)             the same with the count left on the device
     TiledDetector.detect_files(paths) -> iterator of (path, Tensor[n, 7])           scene i + 1 decoded / uploaded while scene i runs
     write_dota_task1({name: dets}, out_dir, class_names)                            DOTA Task1 files (Task1_<class>.txt)
@@ -21,8 +22,16 @@ Views (test-time orientation ensembling; an overhead scene has no preferred orie
 are windows x views, window-major (entry e = window_index * len(views) + view_index), so the views of one window are cut back to back.
 ryolo_tile_cut_views writes an entry's window in its view (flips by index arithmetic, the transposing views through LDS) and
 ryolo_tile_collect_views maps the view's boxes back to the window (point, theta wrapped into [-pi/2, pi/2)) in front of the shift; the
-candidate slot is e * mk + j and the merge is unchanged: it keeps the best-scoring box of a cluster (no score fusion across views).
+candidate slot is e * mk + j and the merge is unchanged: it keeps the best-scoring box of a cluster.
 The definition of the eight views is in include/ryolo.h.
+
+Fusion (fuse="box" | "wbf", default None = the merge above, bit for bit): what makes the extra replays of rates x views pay beyond
+recall.  After the NMS, ryolo_nms_owner reads from the NMS's own suppression mask which kept box removed each suppressed one (no second
+IoU), and ryolo_tile_fuse, in place of ryolo_tile_mark, lets every kept box absorb its cluster: score-weighted centre, size and angle,
+with theta taken modulo pi and (w, h, theta) ~ (h, w, theta +- pi/2) resolved against the kept box; "wbf" also replaces the score by the
+mean member score scaled by min(members, n) / n, n = len(rates) * len(views), so a box seen by one view of eight no longer keeps its
+full score.  The fused rows go to their own buffer (the candidates are only read) and the final order is taken over the fused scores.
+Two more launches per scene, no host read, and no allocation after a plan's first fused merge (which allocates the two buffers).  The arithmetic is defined in include/ryolo.h.
 """
 import math
 from collections import OrderedDict
@@ -52,6 +61,17 @@ def check_views(views):
     if len(set(views)) != len(views):
         raise ValueError(f"views must not repeat, got {views}")
     return views
+
+
+# cluster fusion of the merge; a mode's code for ryolo_tile_fuse is its index here (include/ryolo.h)
+FUSE = ("box", "wbf")
+
+
+def check_fuse(fuse):
+    """-> None, "box" or "wbf", validated."""
+    if fuse is None or (isinstance(fuse, str) and fuse in FUSE):
+        return fuse
+    raise ValueError(f"fuse must be None or one of {FUSE}, got {fuse!r}")
 
 
 # ------------------------------------------------------------------------------------------ window plan
@@ -175,6 +195,10 @@ class ScenePlan:
         self.forder = torch.empty((1, self.Kf), dtype=i64, device=dev)
         self.num = torch.empty(1, dtype=i32, device=dev)
         self.out = torch.empty((self.max_det, 7), dtype=f32, device=dev)
+        # cluster fusion (merge(..., fuse=...)): the owner of every sorted position and the fused rows, by candidate slot.  Allocated by
+        # the first fused merge of the plan, so a detector that never fuses holds exactly the buffers it always held
+        self.n_ens = len(det.rates) * len(self.views)
+        self.owner = self.fused = None
 
     def cut(self, scene, g, dst):
         """Group g's entries of the scene at device address `scene` -> dst [batch, 3, size, size] (slots past the last entry untouched)."""
@@ -192,18 +216,33 @@ class ScenePlan:
             hip.call("ryolo_tile_collect_views", hip.ptr(dets), hip.ptr(num), B, self.mk, hip.ptr(self.geom), g * B, self.T, self.nc,
                      self.ld, self.size, hip.ptr(self.cand), hip.ptr(self.key), hip.ptr(self.fkey), hip.stream())
 
-    def merge(self, merge_iou, gt_only=True):
-        """Class-wise rotated NMS over every collected candidate, then the final order -> (out [max_det, 7], num [1]) on the device."""
+    def merge(self, merge_iou, gt_only=True, fuse=None):
+        """Class-wise rotated NMS over every collected candidate, then the final order -> (out [max_det, 7], num [1]) on the device.
+        fuse None: a kept box is emitted as it is.  "box" / "wbf": it absorbs the boxes it suppressed (ryolo_nms_owner + ryolo_tile_fuse
+        in place of ryolo_tile_mark, the rows emitted from `fused`); the candidates are only read, so the modes can follow each other on
+        the same collected scene."""
+        fuse = check_fuse(fuse)
         nc, Kc, Kf, st = self.nc, self.Kc, self.Kf, hip.stream()
         hip.call("ryolo_topk_desc", hip.ptr(self.key), nc, self.ld, Kc, hip.ptr(self.skey), hip.ptr(self.order), hip.ptr(self.nsel), hip.ptr(self.sort_ws),
                  self.sort_ws.numel(), st)
         hip.call("ryolo_tile_merge_gather", hip.ptr(self.cand), hip.ptr(self.skey), hip.ptr(self.order), nc, Kc, hip.ptr(self.rboxes), st)
         hip.call("ryolo_nms_rotated_batched", hip.ptr(self.rboxes), hip.ptr(self.nsel), nc, Kc, merge_iou, 1 if gt_only else 0, Kc,
                  hip.ptr(self.nms_ws), self.nms_ws.numel(), hip.ptr(self.keep), Kc, hip.ptr(self.nkeep), st)
-        hip.call("ryolo_tile_mark", hip.ptr(self.skey), hip.ptr(self.order), hip.ptr(self.keep), hip.ptr(self.nkeep), nc, Kc, Kc, hip.ptr(self.fkey), st)
+        if fuse is None:
+            hip.call("ryolo_tile_mark", hip.ptr(self.skey), hip.ptr(self.order), hip.ptr(self.keep), hip.ptr(self.nkeep), nc, Kc, Kc, hip.ptr(self.fkey), st)
+            rows = self.cand
+        else:
+            if self.fused is None:
+                self.owner = torch.empty((nc, Kc), dtype=torch.int32, device=self.cand.device)
+                self.fused = torch.empty((self.ld, 7), dtype=torch.float32, device=self.cand.device)
+            hip.call("ryolo_nms_owner", hip.ptr(self.nsel), nc, Kc, hip.ptr(self.nms_ws), self.nms_ws.numel(), hip.ptr(self.keep), Kc,
+                     hip.ptr(self.nkeep), hip.ptr(self.owner), st)
+            hip.call("ryolo_tile_fuse", hip.ptr(self.cand), hip.ptr(self.order), hip.ptr(self.nsel), hip.ptr(self.keep), hip.ptr(self.nkeep),
+                     hip.ptr(self.owner), nc, Kc, Kc, self.ld, FUSE.index(fuse), self.n_ens, hip.ptr(self.fused), hip.ptr(self.fkey), st)
+            rows = self.fused
         hip.call("ryolo_topk_desc", hip.ptr(self.fkey), 1, self.ld, Kf, hip.ptr(self.fskey), hip.ptr(self.forder), hip.ptr(self.num), hip.ptr(self.sort_ws),
                  self.sort_ws.numel(), st)
-        hip.call("ryolo_tile_emit", hip.ptr(self.cand), hip.ptr(self.forder), hip.ptr(self.num), self.max_det, hip.ptr(self.out), st)
+        hip.call("ryolo_tile_emit", hip.ptr(rows), hip.ptr(self.forder), hip.ptr(self.num), self.max_det, hip.ptr(self.out), st)
         return self.out, self.num
 
 
@@ -226,12 +265,16 @@ class TiledDetector:
     class-wise rotated NMS of the merge.  rates: the scene is resized once per rate (INTER_AREA below 1, INTER_LINEAR above; rate 1 is cut
     straight from the scene) and every resized copy is tiled; boxes are mapped back to the original scene.  max_nms: candidates per class
     entering the merge; max_det: detections per scene.  views: names from VIEWS, in the order their entries take inside a window; every
-    window runs once per view and all views' boxes enter the one merge, which keeps the best-scoring box of a cluster."""
+    window runs once per view and all views' boxes enter the one merge, which keeps the best-scoring box of a cluster.  fuse: None
+    emits that box as it is; "box" replaces its geometry by the score-weighted rotated mean of the cluster it suppressed (box voting),
+    score unchanged; "wbf" does the same and sets the score to the mean member score times min(members, n) / n, n = len(rates) *
+    len(views) (weighted box fusion).  The arithmetic is defined in include/ryolo.h (ryolo_tile_fuse)."""
 
     def __init__(self, model, size=1024, overlap=200, batch=8, conf_thres=0.1, iou_thres=0.4, merge_iou=None, rates=(1.0,), max_nms=5000,
-                 max_det=5000, gt_only=True, views=("id",)):
+                 max_det=5000, gt_only=True, views=("id",), fuse=None):
         rates = tuple(float(r) for r in rates)
         views = check_views(views)
+        self.fuse = check_fuse(fuse)                                     # read per scene, like views and rates
         tile_plan(size, size, size, overlap, rates)                      # argument validation
         if int(batch) < 1:
             raise ValueError(f"TiledDetector: batch must be >= 1, got {batch}")
@@ -281,6 +324,7 @@ class TiledDetector:
 
     # ---- the device pipeline of one scene
     def _enqueue(self, placed):
+        fuse = check_fuse(self.fuse)                                     # a bad mode set on the detector fails before anything is launched
         H, W = placed.H, placed.W
         p = self.plan(H, W)
         st = hip.stream()
@@ -304,7 +348,7 @@ class TiledDetector:
             p.cut(scene, g, run.static_input)
             run.graph.replay()
             p.collect(run.post_plan.out, run.post_plan.num, g)
-        return p.merge(self.merge_iou, self.gt_only)
+        return p.merge(self.merge_iou, self.gt_only, fuse)
 
     # ---- public
     def run_async(self, scene):

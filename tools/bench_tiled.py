@@ -9,7 +9,8 @@ one JSON line:
                                   post, post_process per group, a host-side shift, per-class nms_rotated
   files_overlap_ms / files_serial_ms   detect_files over 8 scenes with / without the side-stream upload overlap (decode = an in-memory copy)
 The naive loop has no views: naive_ms and speedup_vs_naive compare like with like only for VIEWS=id.
-Environment: SCENE (4000), S (1024), OVERLAP (200), B (8), CONF (0.1), N (iterations, 10), VIEWS (comma list of lib.tiled.VIEWS names, id)."""
+Environment: SCENE (4000), S (1024), OVERLAP (200), B (8), CONF (0.1), N (iterations, 10), VIEWS (comma list of lib.tiled.VIEWS names, id),
+FUSE (box | wbf: cluster fusion in the merge; unset = none)."""
 import json
 import os
 import sys
@@ -28,11 +29,12 @@ dev = torch.device("cuda:0")
 SC, S, OV, B = int(os.environ.get("SCENE", 4000)), int(os.environ.get("S", 1024)), int(os.environ.get("OVERLAP", 200)), int(os.environ.get("B", 8))
 CONF, IOU, N = float(os.environ.get("CONF", 0.1)), 0.4, int(os.environ.get("N", 10))
 VIEWS = tuple(v.strip() for v in os.environ.get("VIEWS", "id").split(",") if v.strip())
+FUSE = os.environ.get("FUSE", "").strip() or None
 
 net = Yolo(16, CFG, "kfiou", "yolov7")
 net.load_state_dict(fill_state(net.state_dict()))
 net.to(dev).eval()
-det = TiledDetector(net, size=S, overlap=OV, batch=B, conf_thres=CONF, iou_thres=IOU, views=VIEWS)
+det = TiledDetector(net, size=S, overlap=OV, batch=B, conf_thres=CONF, iou_thres=IOU, views=VIEWS, fuse=FUSE)
 scene = np.random.RandomState(0).randint(0, 256, (SC, SC, 3)).astype(np.uint8)
 scene_dev = torch.from_numpy(scene).to(dev)
 wins = tile_plan(SC, SC, S, OV)
@@ -110,7 +112,7 @@ t_naive = wall(naive, max(2, N // 3))
 t_fo = wall(lambda: run_files(True), 2) / len(files)
 t_fs = wall(lambda: run_files(False), 2) / len(files)
 n_tiled, n_naive = tiled(), naive()
-print(json.dumps({"scene": SC, "S": S, "overlap": OV, "batch": B, "views": list(VIEWS), "windows": len(wins), "entries": entries, "groups": egroups,
+print(json.dumps({"scene": SC, "S": S, "overlap": OV, "batch": B, "views": list(VIEWS), "fuse": FUSE, "windows": len(wins), "entries": entries, "groups": egroups,
                   "padded_slots": egroups * B - entries,
                   "conf_thres": CONF, "detections": n_tiled, "naive_detections": n_naive,
                   "scene_ms": round(t_scene, 3), "entry_ms": round(t_scene / entries, 3), "windows_per_s": round(len(wins) / t_scene * 1e3, 1), "replay_ms": round(t_rep, 3),
