@@ -162,6 +162,13 @@ int ryolo_conv_wgrad(const WgradParams* p, ryolo_stream_t stream);
  * 256 x 256-tile pointwise kernel (stride-1 1x1 layers with Cin >= 256 and Cout > 128; needs p->zeros).  (4, the parity-plane ring kernel for 3x3
  * stride-2 layers, was retired in round 6 and is no longer returned.)  Answers RY_OK with kernel 0 also for blocks ryolo_conv_wgrad rejects. */
 int ryolo_conv_wgrad_kernel(const WgradParams* p, int* kernel);
+/* which instantiation of that kernel, from the same decision the launch switches on (host only, like the plan).  *word & 0xff = the kernel code above;
+ * kernel 0: bits 8-11 = output-channel tile / 64 (1: conv_wgrad_kernel<64, .>, 2: the 128-channel tiles), bits 12-15 = 0 register-staged with tap
+ * addressing, 1 register-staged with pointwise addressing (conv_wgrad_kernel<., true>), 2 wgrad1x1_dma_kernel<32>, 3 wgrad1x1_dma_kernel<64>;
+ * kernel 1: bits 8-11 = 0 the 4-wave kernels, 2 / 4 conv3x3_wgrad8_kernel<2 | 4>, bits 12-15 = its prefetch steps (1 or 2; 0 on 4 waves),
+ * bit 16 = 64-pixel K steps (conv3x3_wgrad64_kernel; always set on 8 waves), bit 17 = the <= 64 output-channel form (two slabs per K range),
+ * bit 18 = mirrored ring head; kernels 2 and 3 have one instantiation each (no further bits).  Returns the status ryolo_conv_wgrad_plan returns. */
+int ryolo_conv_wgrad_variant(const WgradParams* p, int* word);
 /* launch shape of that kernel: workgroups, waves per workgroup (8: a workgroup holds its CU exclusively and the grid is sized to part of the chip) */
 int ryolo_conv_wgrad_grid(const WgradParams* p, int* workgroups, int* waves);
 /* weights of a stride-2 3x3 (pad 1) data gradient in its space-to-depth form (ConvGemmParams.s2d_cin): w fp32 [Cout][Cin][3][3] ->

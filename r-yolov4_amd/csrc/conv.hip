@@ -1754,6 +1754,22 @@ extern "C" int ryolo_conv_wgrad_kernel(const WgradParams* pp, int* kernel)
     return RY_OK;
 }
 
+// which INSTANTIATION ryolo_conv_wgrad will launch, from the same route (bit layout: ryolo.h).  Tests assert it so that a case names the template
+// arguments it covers; the status is the route's (a rejected block has no instantiation).
+extern "C" int ryolo_conv_wgrad_variant(const WgradParams* pp, int* word)
+{
+    if (!pp || !word) return RY_ERR_ARG;
+    WgradParams p = *pp;
+    WgradRoute r;
+    const int rc = wgrad_route(p, r);
+    int w = r.kernel;
+    if (r.kernel == WGRAD_GENERIC) w |= ((r.bm / 64) << 8) | (r.variant << 12);
+    else if (r.kernel == WGRAD_RING3)
+        w |= (r.g3.v8 << 8) | (r.g3.pd << 12) | (r.g3.step64 ? 1 << 16 : 0) | (r.g3.co64 ? 1 << 17 : 0) | (r.g3.mirror ? 1 << 18 : 0);
+    *word = w;
+    return rc;
+}
+
 // launch shape of the split-K kernel ryolo_conv_wgrad will use: workgroups and waves per workgroup.  The 8-wave kernels (conv3x3_wgrad8.hip,
 // wgrad1x1_8w.hip) hold a CU exclusively (2 x ~200+ registers per SIMD lane, 76-150 KiB of LDS) and are sized to PART of the chip: a launch timed
 // alone then occupies `workgroups` of the 256 CUs — bench.py prices such a launch against the CUs it holds as well as against the whole chip.

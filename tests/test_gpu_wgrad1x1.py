@@ -3,7 +3,8 @@ through the C ABI against a float64 weight gradient on the same bf16 operands (m
 nn.Conv2d w.r.t. its weight).  Ragged tiles on both channel axes (Cout = 396 = the merged head width of the bench network, Cin = 320), channel
 strides wider than the tensors (concat slices), K ranges that end inside a 64-pixel step, accumulation into an existing gradient; dispatch is
 asserted (kernel 3), narrower layers stay on the 4-wave kernels by default (the idle-wave form of the 8-wave kernel is tested behind its knob).  Tolerance 2e-5 relative against the float64 product of
-the same bf16 operands (tests/wgrad_ref.py; measured 2e-7).  The 4-wave kernels keep their coverage for these shapes through RYOLO_WGRAD_8W=0 in tests/test_gpu_forced_kernels.py."""
+the same bf16 operands (tests/wgrad_ref.py; measured 2e-7).  The 4-wave kernels keep their coverage for these shapes through RYOLO_WGRAD_8W=0 in tests/test_gpu_forced_kernels.py.
+Exactness (ragged tiles, K-range ends, idle waves, dW2) is pinned bit for bit on integer lattices in tests/test_gpu_wgrad_lattice.py."""
 import pytest
 
 from tests.test_gpu_wgrad_taps import _run

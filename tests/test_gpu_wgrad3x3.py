@@ -9,7 +9,10 @@ Round 5: layers with Cin % 64 == 0 run on the 8-wave form (csrc/conv3x3_wgrad8.h
 length with a mirrored head) by default — the cases below with Cin 64 / 128 / 192 / 256 exercise both of its instantiations (<= 64 output
 channels: pixel halves + two slabs; 128-channel tiles: output-channel pairs), ring wrap-around over many laps (long K ranges on narrow maps),
 maps as wide as its LDS budget allows, ragged Cout, concat strides; Cin = 32 stays on the 4-wave kernels, and the whole file runs once more
-with RYOLO_W3_V8=0 in tests/test_gpu_forced_kernels.py so that those keep their coverage for every shape."""
+with RYOLO_W3_V8=0 in tests/test_gpu_forced_kernels.py so that those keep their coverage for every shape.
+
+Exactness (ring laps, K-range ends, image seams, ragged quarters, every instantiation by name) is pinned bit for bit on integer lattices in
+tests/test_gpu_wgrad_lattice.py; the norm here answers for fp32 rounding at workload sizes."""
 import pytest
 import torch
 
