@@ -429,6 +429,37 @@ int ryolo_tile_fuse(const float* cand, const int64_t* order, const int32_t* nsel
 /* order [>= num[0]] = ryolo_topk_desc of fkey, num [1] its selection count -> out [max_det, 7] = cand[order[j]] for j < num[0], zeros after */
 int ryolo_tile_emit(const float* cand, const int64_t* order, const int32_t* num, int64_t max_det, float* out, ryolo_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Training on full-size scenes (csrc/scene.hip; datasets/scene_dataset.py): the source image of a sample is a WINDOW of a scene in the
+ * pool.  The reference has no such stage (it trains on windows cut offline); tests/scene_ref.py restates these semantics in numpy.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* ryolo_resize_hsv_batch through a window: `items` = device array of nitems records {int64 src_off, dst_off; int SH, SW, NH, NW, interp, lut,
+ * x0, y0, c, pad} (ryolo_window_item_bytes = sizeof): the SH x SW scene at pool + src_off (4-byte aligned for the wide copy path; any
+ * alignment is correct), the window [x0, x0 + c) x [y0, y0 + c) in scene pixels, which may hang over any border (negative origins
+ * included) or miss the scene.  BIT-IDENTICAL to cutting the c x c window first (114 wherever it lies outside the scene) and running
+ * ryolo_resize_hsv_batch on the cut with {SH = SW = c, NH, NW, interp, lut}: copy, the exact 2 x integer block path, generic INTER_LINEAR, both
+ * INTER_AREA forms, taps that straddle the scene border.  No intermediate cut is written.  The copy path (interp 2, NH = NW = c) moves 16
+ * pixels per thread with 16-byte loads and stores, realigning the arbitrary source row start in registers; it never reads past the scene's
+ * last byte.  dst_off multiples of 16 (what datasets/augment.py lays out) get the wide stores.  The copy path never consults c: an item with
+ * interp 2 and (NH, NW) != (c, c) copies the NH x NW window at (x0, y0), with the same fill and the same bounds on every access. */
+int ryolo_window_item_bytes(int* bytes);
+int ryolo_resize_hsv_windows(const uint8_t* pool, const void* items_dev, int nitems, int64_t max_pixels, const uint8_t* luts, uint8_t* stage,
+                             ryolo_stream_t stream);
+/* Which labels of a scene belong to a window — IN PLACE on an uploaded LabelRow table (before ryolo_label_stage) whose polygons are in scene
+ * pixels; row i belongs to window wins[win_of_row[i]], wins int32 [nwin][3] = (x0, y0, c), |x0|, |y0|, c < 2^24.  A row whose index is outside
+ * [0, nwin) is dropped (poly = NaN, IoF 0, w0 / h0 untouched) without reading `wins`.  Per row:
+ *   shift   p' = fl32(p - origin) per coordinate, fp32;
+ *   clip    in fp64, the quad p' against [0, c]^2 by Sutherland-Hodgman, planes in the order x >= 0, x <= c, y >= 0, y <= c (a vertex on a
+ *           plane is inside); a crossing on edge a -> b is t = (bound - a_k) / (b_k - a_k), the other coordinate a_o + t (b_o - a_o), the
+ *           clipped coordinate the bound itself;
+ *   ratio   IoF = min(1, |shoelace(clipped)| / |shoelace(quad)|), shoelace = sum of (x_k y_k+1 - x_k+1 y_k) in vertex order, left to right;
+ *           either orientation.  |shoelace(quad)| <= 0 (or NaN): the row is dropped and reports IoF 0;
+ *   result  IoF >= iof_thr: poly = p' (NOT clipped: the filters downstream handle polygons that reach past a canvas); otherwise poly = NaN,
+ *           which ryolo_label_stage carries and ryolo_encode_labels removes in order.  w0 = h0 = c for every row.
+ * iof_out (optional): double [nrows].  0 < iof_thr <= 1.  The host leaves out labels whose bounding box misses the window (IoF 0). */
+int ryolo_scene_label_rows(void* rows_dev, int64_t nrows, const int32_t* win_of_row, const int32_t* wins, int nwin, double iof_thr,
+                           double* iof_out, ryolo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

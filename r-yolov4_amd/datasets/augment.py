@@ -295,6 +295,11 @@ class _ResizeItem(ctypes.Structure):
     _fields_ = [("src_off", _L), ("dst_off", _L), ("SH", _I), ("SW", _I), ("NH", _I), ("NW", _I), ("interp", _I), ("lut", _I)]
 
 
+class _WindowItem(ctypes.Structure):      # csrc/scene.hip: _ResizeItem of a window's c x c cut + where the cut lies in its scene (SH, SW)
+    _fields_ = [("src_off", _L), ("dst_off", _L), ("SH", _I), ("SW", _I), ("NH", _I), ("NW", _I), ("interp", _I), ("lut", _I), ("x0", _I), ("y0", _I),
+                ("c", _I), ("pad_", _I)]
+
+
 class _LabelRow(ctypes.Structure):
     _fields_ = [("poly", ctypes.c_float * 8), ("cls", ctypes.c_float), ("slot", _I), ("w0", ctypes.c_float), ("h0", ctypes.c_float),
                 ("w1", ctypes.c_float), ("h1", ctypes.c_float), ("bx1", ctypes.c_float), ("bx2", ctypes.c_float), ("by1", ctypes.c_float),
@@ -315,7 +320,8 @@ def _check_layouts():
     if _checked:
         return
     n = _I()
-    for name, t in (("ryolo_paste_rect_bytes", _Rect), ("ryolo_resize_item_bytes", _ResizeItem), ("ryolo_label_row_bytes", _LabelRow)):
+    for name, t in (("ryolo_paste_rect_bytes", _Rect), ("ryolo_resize_item_bytes", _ResizeItem), ("ryolo_label_row_bytes", _LabelRow),
+                    ("ryolo_window_item_bytes", _WindowItem)):
         hip.call(name, n)
         if n.value != ctypes.sizeof(t):
             raise RuntimeError(f"ryolov4_amd: struct layout mismatch for {t.__name__}: C {n.value} vs ctypes {ctypes.sizeof(t)}")
@@ -384,14 +390,74 @@ def resize_hsv_batch(pool, items, luts=None):
     return stage, offs
 
 
+WINDOW_COORD_MAX = 1 << 24                # window origins and sides are exact as fp32 (the label shift) and far from int32 overflow
+
+
+def resize_hsv_windows(pool, items, luts=None):
+    """resize_hsv_batch whose sources are WINDOWS of pool images: items [(pool image index, (x0, y0, c), (NH, NW), interp, lut index or -1)]
+    -> (staging buffer, [byte offset of every result]).  Same bits as resize_hsv_batch on the c x c cut (114 where the window lies outside
+    its image), without the cut pass (csrc/scene.hip)."""
+    _check_layouts()
+    dev = pool.buf.device
+    arr = (_WindowItem * max(len(items), 1))()
+    offs, total, maxpix = [], 0, 0
+    for k, (img, (x0, y0, c), (nh, nw), interp, lut) in enumerate(items):
+        sh, sw = pool.shapes[img]
+        if not (0 < c <= 46340 and max(abs(x0), abs(y0)) < WINDOW_COORD_MAX and 0 < nh and 0 < nw):
+            raise ValueError(f"resize_hsv_windows: window ({x0}, {y0}, {c}) -> {nh} x {nw} out of range")
+        if interp == INTERP_COPY and (nh, nw) != (c, c):
+            raise ValueError("resize_hsv_windows: a copied window keeps its size")
+        arr[k] = _WindowItem(pool.offsets[img], total, sh, sw, nh, nw, interp, lut, x0, y0, c, 0)
+        offs.append(total)
+        total += ((nh * nw * 3 + 15) // 16) * 16
+        maxpix = max(maxpix, nh * nw)
+    stage = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+    if items:
+        lt = None if luts is None or not len(luts) else _to_device(np.ascontiguousarray(luts, dtype=np.uint8), dev)
+        hip.call("ryolo_resize_hsv_windows", hip.ptr(pool.buf), hip.ptr(_to_device(arr, dev)), len(items), maxpix, hip.ptr(lt), hip.ptr(stage),
+                 hip.stream())
+    return stage, offs
+
+
+def upload_label_rows(rows, device):
+    """LABEL_ROW_DTYPE rows -> their device table (uint8), what label_stage_table and scene_label_rows work on."""
+    _check_layouts()
+    return _to_device(np.frombuffer(rows.tobytes(), dtype=np.uint8), device)
+
+
+def scene_label_rows(table, nrows, win_of_row, wins, iof_thr, want_iof=False):
+    """In place on an uploaded LabelRow table whose polygons are in SCENE pixels: row i belongs to window wins[win_of_row[i]] = (x0, y0, c);
+    its polygon is shifted by the window origin (fp32) and kept when intersection-over-foreground with [0, c]^2 (fp64 Sutherland-Hodgman)
+    reaches iof_thr, otherwise set to NaN; w0 = h0 = c.  want_iof: returns the IoF per row (float64, device)."""
+    _check_layouts()
+    dev = table.device
+    wins = np.ascontiguousarray(wins, dtype=np.int64).reshape(-1, 3)
+    win_of_row = np.ascontiguousarray(win_of_row, dtype=np.int32).reshape(-1)
+    if len(win_of_row) != nrows or (nrows and (win_of_row.min() < 0 or win_of_row.max() >= len(wins))):
+        raise ValueError("scene_label_rows: one valid window index per row")
+    if len(wins) and (np.abs(wins).max() >= WINDOW_COORD_MAX or wins[:, 2].min() <= 0):
+        raise ValueError("scene_label_rows: window out of range")
+    iof = torch.empty(max(nrows, 1), dtype=torch.float64, device=dev) if want_iof else None
+    if nrows:
+        # (both tables stay referenced until the call is enqueued: a temporary inside the argument list is freed as soon as its pointer
+        # is taken, and the next upload would get its block)
+        wor_dev, wins_dev = _to_device(win_of_row, dev), _to_device(wins.astype(np.int32), dev)
+        hip.call("ryolo_scene_label_rows", hip.ptr(table), nrows, hip.ptr(wor_dev), hip.ptr(wins_dev), len(wins), float(iof_thr), hip.ptr(iof),
+                 hip.stream())
+    return None if iof is None else iof[:nrows]
+
+
 def label_stage(rows, mats, device):
     """rows: numpy structured array (LABEL_ROW_DTYPE), mats: [n, 3, 3] float64 warp matrices (or empty) -> targets10 [nrows, 10] on the
     device = (slot, class, 8 vertex coordinates), NaN vertices for rows a filter dropped (ryolo_encode_labels removes them in order)."""
+    return label_stage_table(upload_label_rows(rows, device) if len(rows) else None, len(rows), mats, device)
+
+
+def label_stage_table(table, n, mats, device):
+    """label_stage on a table of n rows that is already on the device (upload_label_rows; None when n == 0)."""
     _check_layouts()
-    n = len(rows)
     out = torch.empty((n, 10), dtype=torch.float32, device=device)
     if n:
-        table = _to_device(np.frombuffer(rows.tobytes(), dtype=np.uint8), device)
         mt = None if mats is None or not len(mats) else _to_device(np.ascontiguousarray(mats, dtype=np.float64).reshape(-1, 9), device).view(torch.float64)
         hip.call("ryolo_label_stage", hip.ptr(table), n, hip.ptr(mt), hip.ptr(out), hip.stream())
     return out

@@ -133,16 +133,18 @@ class BaseDataset:
         per-batch collective, so unequal shard lengths are harmless there."""
         if self._pool is not None:
             raise RuntimeError("BaseDataset.shard: call before the first batch is assembled")
-        pad = self.augment if pad is None else pad
-        n = len(self.img_files)
-        if n:
-            if pad:
-                per = -(-n // world_size)
-                idx = [(rank + k * world_size) % n for k in range(per)]
-            else:
-                idx = list(range(rank, n, world_size))
-            self.img_files, self.label_files = [self.img_files[i] for i in idx], [self.label_files[i] for i in idx]
+        idx = self._shard_indices(len(self.img_files), rank, world_size, self.augment if pad is None else pad)
+        self.img_files, self.label_files = [self.img_files[i] for i in idx], [self.label_files[i] for i in idx]
         return self
+
+    @staticmethod
+    def _shard_indices(n, rank, world_size, pad):
+        if not n:
+            return []
+        if pad:
+            per = -(-n // world_size)
+            return [(rank + k * world_size) % n for k in range(per)]
+        return list(range(rank, n, world_size))
 
     def __len__(self):
         return len(self.img_files)
@@ -169,11 +171,11 @@ class BaseDataset:
         file headers (`imsize`) so that planning a batch does not need pixels.  Datasets over the same files on the same device share
         one pool (test.py calls load_data for every evaluation)."""
         if self._pool is None:
-            files = self.img_files
+            files, label_files = self._pool_files()
             # the key holds the decoder OBJECT (a reference: an id() could be reused after garbage collection) and everything the parsed
             # labels depend on — label files, the class list of the concrete dataset, the label convention — so two datasets over the same
             # images with different classes or label directories never see each other's class indices
-            key = (tuple(files), tuple(self.label_files), tuple(getattr(self, "category", None) or ()), type(self).__name__, bool(self.normalized_labels),
+            key = (tuple(files), tuple(label_files), tuple(getattr(self, "category", None) or ()), type(self).__name__, bool(self.normalized_labels),
                    str(self.device), self.pool_budget_bytes, self.pool_slab_bytes, self.imread)
             if self.share_pool and key in _POOL_CACHE:
                 self._pool, self._labels = _POOL_CACHE[key]
@@ -192,19 +194,48 @@ class BaseDataset:
         """(polys float32 [n, 8], classes float32 [n]) of image `index`, parsed on first use."""
         got = self._labels.get(index)
         if got is None:
-            lp = self.label_files[index].rstrip()
-            assert os.path.exists(lp), "Label file {} not found".format(lp)          # base_dataset.py:221
-            p, c = self.load_files(lp)
-            p = p.numpy() if isinstance(p, torch.Tensor) else p
-            c = c.numpy() if isinstance(c, torch.Tensor) else (c if len(c) else np.zeros(0, np.float32))
-            got = self._labels[index] = (np.asarray(p, dtype=np.float32).reshape(-1, 8), np.asarray(c, dtype=np.float32).reshape(-1))
+            got = self._labels[index] = self._parse_label_file(self.label_files[index])
         return got
+
+    def _parse_label_file(self, label_path):
+        lp = label_path.rstrip()
+        assert os.path.exists(lp), "Label file {} not found".format(lp)          # base_dataset.py:221
+        p, c = self.load_files(lp)
+        p = p.numpy() if isinstance(p, torch.Tensor) else p
+        c = c.numpy() if isinstance(c, torch.Tensor) else (c if len(c) else np.zeros(0, np.float32))
+        return np.asarray(p, dtype=np.float32).reshape(-1, 8), np.asarray(c, dtype=np.float32).reshape(-1)
+
+    # ------------------------------------------------------------------ what a subclass whose samples are not whole pool images overrides
+    # (datasets/scene_dataset.py: a sample's source is a window of a scene); the bodies here are the statements assemble_batch always ran
+    def _pool_files(self):
+        """(image files, label files) the pool and the parsed-label cache are built over."""
+        return self.img_files, self.label_files
+
+    def _use_shape(self, index, row):
+        """(h0, w0) of the source image of the use that becomes row `row` of the resize table.  Contract: _load_image_plan calls this exactly
+        once per use, in row order, immediately before it appends that row; an override may therefore draw per use and keep per-row state
+        of its own (SceneDataset draws the window origin here and records it as row `row` of `last_windows`)."""
+        return self._pool.shapes[index]
+
+    def _use_labels(self, index, row):
+        """(polys, classes) that go into the label table for that use."""
+        return self.labels_of(index)
+
+    def _pixel_stage(self, pool, items, luts):
+        """items [(dataset index, (h, w), interp, lut)] -> (staging buffer, byte offset per row): load_image's resize + hsv."""
+        pool.ensure(it[0] for it in items)                        # decode + upload what is not resident (this batch's slabs are protected)
+        return A.resize_hsv_batch(pool, items, luts)
+
+    def _label_table(self, rows):
+        """The LabelRow rows of a batch (never empty) -> their device table: called once per batch between building the rows and
+        ryolo_label_stage."""
+        return A.upload_label_rows(rows, self.device)
 
     # ------------------------------------------------------------------ the draws, in the reference's order
     def _load_image_plan(self, index, items, luts):
         """load_image (base_dataset.py:170-186) as a table row: resized size, interpolation, the hsv tables of this use.
         Returns (row index into `items`, (h0, w0), (h, w))."""
-        h0, w0 = self._pool.shapes[index]
+        h0, w0 = self._use_shape(index, len(items))
         r = self.img_size / max(h0, w0)
         h, w, interp = h0, w0, A.INTERP_COPY
         if r != 1:
@@ -278,8 +309,7 @@ class BaseDataset:
             if self.augment and nrd.random() < self.hyp["flipud"]:
                 flags[slot] |= 2
         # ---- pixels -----------------------------------------------------------------------------------------------------------------
-        pool.ensure(it[0] for it in items)                        # decode + upload what is not resident (this batch's slabs are protected)
-        stage, offs = A.resize_hsv_batch(pool, items, np.stack(luts) if luts else None)
+        stage, offs = self._pixel_stage(pool, items, np.stack(luts) if luts else None)
         final = torch.empty((B, s, s, 3), dtype=torch.uint8, device=dev)
         mos = [c for c in canvases if c["kind"] == "mosaic"]
         warped = {}
@@ -316,16 +346,16 @@ class BaseDataset:
                 mats.append(c["M"])
             if c["kind"] == "mosaic":
                 for u, ds_index, hw0, hw in c["uses"]:
-                    polys, cls = self.labels_of(ds_index)
+                    polys, cls = self._use_labels(ds_index, u.img)
                     rows.append(A.label_rows(polys, cls, c["slot"], hw0, hw, u, mat, self.normalized_labels))
             else:
-                polys, cls = self.labels_of(c["index"])
+                polys, cls = self._use_labels(c["index"], c["item"])
                 u = A.Use(c["item"], None, c["pad"], None, None)
                 rows.append(A.label_rows(polys, cls, c["slot"], c["hw0"], c["hw"], u, mat, self.normalized_labels))
         rows = np.concatenate(rows) if rows else np.zeros(0, dtype=A.LABEL_ROW_DTYPE)
         # (mixup appends the second canvas' labels behind the first's: canvases of one sample are adjacent and in that order; samples are
         # in slot order, so the rows are already ordered the way collate_fn's torch.cat orders them)
-        targets10 = A.label_stage(rows, np.stack(mats) if mats else None, dev)
+        targets10 = A.label_stage_table(self._label_table(rows) if len(rows) else None, len(rows), np.stack(mats) if mats else None, dev)
         imgs, targets = finalize_batch(final, targets10, A._to_device(flags, dev), self.csl)
         return [self.img_files[i] for i in indices], imgs, targets
 

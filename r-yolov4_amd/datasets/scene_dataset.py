@@ -1,0 +1,230 @@
+"""Training and validation on full-size labelled scenes: the windows are cut on the device, batch by batch.
+
+The reference trains on windows that an external devkit cut offline (data/DOTA.yaml: data/DOTA/split/train); it has no code for this
+stage, as it has none for tiled detection (lib/tiled.py).  Here a dataset ITEM is a planned window of a scene; the ImagePool holds the
+scenes, and the first stage of BaseDataset.assemble_batch — the source image of a use and the labels that belong to it — reads through
+the window (csrc/scene.hip):
+
+    ryolo_resize_hsv_windows   load_image's resize + hsv of the window, bit-identical to ryolo_resize_hsv_batch on the c x c cut
+                               (114 where the window lies outside the scene), without a cut pass;
+    ryolo_scene_label_rows     shift by the window origin, keep a label when intersection-over-foreground with the window reaches
+                               `iof_thr`; dropped rows become NaN rows, which the rest of the chain already removes in order.
+
+Everything downstream (mosaic / mixup / warp / hsv, the draws from `rng` in the reference's order, label_stage, encode_labels) is
+BaseDataset's, unchanged.  With `jitter` every use of an item redraws its window origin from a private random.Random(window_seed), so
+the crop positions are not fixed for the run as an offline split fixes them.  tests/scene_ref.py restates the semantics in numpy.
+"""
+import glob
+import math
+import os
+import random as _py_random
+
+import numpy as np
+
+from . import augment as A
+from .base_dataset import BaseDataset
+from .DOTA_dataset import DOTADataset
+from ..lib.tiled import _starts
+
+
+def scene_windows(H, W, size, overlap, rates=(1.0,)):
+    """Planned windows of an H x W scene in SCENE pixels: [(rate_index, x0, y0, c)], ordered by rate, then y0, then x0.  At rate r a
+    window has side c = int(size / r + 0.5) (it is resized to size x size by the pixel stage) and the stride is c - int(overlap / r +
+    0.5); starts along an axis as lib/tiled.py places them (an axis no longer than c: the single start 0, the window hangs over the
+    scene).  rates=(1.0,) gives tiled.tile_plan's windows with c = size."""
+    if not isinstance(size, (int, np.integer)) or size <= 0 or size % 32:
+        raise ValueError(f"scene_windows: size must be a positive multiple of 32 (the largest head stride), got {size}")
+    if not isinstance(overlap, (int, np.integer)) or not 0 <= overlap < size:
+        raise ValueError(f"scene_windows: overlap must satisfy 0 <= overlap < size, got {overlap}")
+    rates = tuple(rates)
+    if not rates or any(not (float(r) > 0) or not math.isfinite(float(r)) for r in rates):
+        raise ValueError(f"scene_windows: rates must be positive, got {rates}")
+    if int(H) <= 0 or int(W) <= 0:
+        raise ValueError(f"scene_windows: empty scene {H} x {W}")
+    out = []
+    for ri, r in enumerate(rates):
+        c = int(size / float(r) + 0.5)
+        stride = c - int(overlap / float(r) + 0.5)
+        if c <= 0 or stride <= 0 or c >= A.WINDOW_COORD_MAX:
+            raise ValueError(f"scene_windows: rate {r} gives a window of {c} pixels with stride {stride}")
+        xs = _starts(int(W), c, stride)
+        for y0 in _starts(int(H), c, stride):
+            out.extend((ri, x0, y0, c) for x0 in xs)
+    return out
+
+
+def jitter_window(wrng, H, W, c, polys, p_object):
+    """One redraw of a window origin in an H x W scene: per axis randint(min(0, L - c), max(0, L - c)) (a scene smaller than the window
+    floats inside it: negative origins).  With probability p_object, if the scene has labels, one label is drawn and the range of each
+    axis is intersected with [ceil(m) - c + 1, floor(m)], m the label's mean vertex (an empty intersection: the whole range).  Draw
+    order: the coin, the label index if drawn, x, y."""
+    rx, ry = (min(0, W - c), max(0, W - c)), (min(0, H - c), max(0, H - c))
+    if wrng.random() < p_object and len(polys):
+        p = polys[wrng.randrange(len(polys))]
+        mx = (float(p[0]) + float(p[2]) + float(p[4]) + float(p[6])) / 4.0
+        my = (float(p[1]) + float(p[3]) + float(p[5]) + float(p[7])) / 4.0
+        ax, bx = max(rx[0], math.ceil(mx) - c + 1), min(rx[1], math.floor(mx))
+        ay, by = max(ry[0], math.ceil(my) - c + 1), min(ry[1], math.floor(my))
+        if ax <= bx:
+            rx = (ax, bx)
+        if ay <= by:
+            ry = (ay, by)
+    x0 = wrng.randint(*rx)
+    return x0, wrng.randint(*ry)
+
+
+def label_boxes(polys):
+    """(min x, max x, min y, max y) per label, float32 [4, n]."""
+    polys = np.asarray(polys, dtype=np.float32).reshape(-1, 8)
+    xs, ys = polys[:, 0::2], polys[:, 1::2]
+    if not len(polys):
+        return np.zeros((4, 0), dtype=np.float32)
+    return np.stack([xs.min(1), xs.max(1), ys.min(1), ys.max(1)])
+
+
+def cull_labels(polys, x0, y0, c, boxes=None):
+    """Indices (file order) of the labels whose axis-aligned bounding box overlaps the window with positive extent; every other label has
+    intersection-over-foreground 0 with it, so leaving it out of the table cannot change a result."""
+    b = label_boxes(polys) if boxes is None else boxes
+    return np.nonzero((b[1] > x0) & (b[0] < x0 + c) & (b[3] > y0) & (b[2] < y0 + c))[0]
+
+
+class SceneDataset(BaseDataset):
+    """BaseDataset whose items are windows of scenes.  Subclasses fill `scene_files` / `scene_label_files`, implement `load_files` and call
+    `plan_windows()`; `set_arrays(scenes, polys, labels)` does the same from decoded scenes.  `img_files` / `label_files` / `len()` are per
+    ITEM ("<scene path>#x0,y0,c"), so the mosaic partner draws range over windows.
+
+    overlap, rates: the window plan (scene_windows, window side = img_size / rate).  iof_thr: a label belongs to a window when that share
+    of its area lies inside.  keep_empty=False: planned windows that keep no label are not items (one launch of ryolo_scene_label_rows over
+    all scenes at construction, label files only — no pixels are decoded).  jitter (default: augment): every USE of an item, mosaic
+    partners included, redraws the window origin (jitter_window) from random.Random(window_seed) — never from `rng`, whose draws stay in
+    the reference's order.  `last_windows`: (item, scene, x0, y0, c) per row of the last batch's resize table."""
+
+    def __init__(self, hyp, img_size, augment, csl, normalized_labels=False, overlap=200, rates=(1.0,), iof_thr=0.7, keep_empty=False,
+                 jitter=None, p_object=0.5, window_seed=0, **device_kw):
+        super().__init__(hyp, img_size, augment, csl, normalized_labels, **device_kw)
+        if normalized_labels:
+            raise ValueError("SceneDataset: scene labels are in scene pixels (normalized_labels=False)")
+        if not (0.0 < float(iof_thr) <= 1.0):
+            raise ValueError(f"SceneDataset: iof_thr must satisfy 0 < iof_thr <= 1, got {iof_thr}")
+        if not (0.0 <= float(p_object) <= 1.0):
+            raise ValueError(f"SceneDataset: p_object is a probability, got {p_object}")
+        scene_windows(1, 1, img_size, overlap, rates)               # argument errors now, not at the first scene
+        self.overlap, self.rates, self.iof_thr, self.keep_empty = overlap, tuple(rates), float(iof_thr), bool(keep_empty)
+        self.jitter = bool(augment) if jitter is None else bool(jitter)
+        self.p_object = float(p_object)
+        self._wrng = _py_random.Random(window_seed)
+        self.scene_files, self.scene_label_files = [], []
+        self.items = []                                            # (scene, rate index, x0, y0, c)
+        self.last_windows, self._row_wins = [], []
+        self._boxes = {}                                           # scene -> label_boxes of its labels (the cull of every use)
+
+    # ------------------------------------------------------------------ the item table
+    def _pool_files(self):
+        return self.scene_files, self.scene_label_files
+
+    def scene_labels(self, scene):
+        """(polys float32 [n, 8] in scene pixels, classes float32 [n]) of a scene, parsed on first use."""
+        got = self._labels.get(scene)
+        if got is None:
+            got = self._labels[scene] = self._parse_label_file(self.scene_label_files[scene])
+        return got
+
+    def _window_labels(self, scene, x0, y0, c):
+        polys, cls = self.scene_labels(scene)
+        boxes = self._boxes.get(scene)
+        if boxes is None:
+            boxes = self._boxes[scene] = label_boxes(polys)
+        keep = cull_labels(polys, x0, y0, c, boxes)
+        return polys[keep], cls[keep]
+
+    def plan_windows(self):
+        """(Re)build the item table from the scenes: every planned window, minus — without keep_empty — those that keep no label."""
+        pool = self.cache()
+        items = []
+        for s in range(len(self.scene_files)):
+            H, W = pool.shapes[s]
+            items += [(s, ri, x0, y0, c) for ri, x0, y0, c in scene_windows(H, W, self.img_size, self.overlap, self.rates)]
+        if not self.keep_empty and items:
+            kept = self._windows_with_labels(items)
+            items = [it for it, k in zip(items, kept) if k]
+        self._set_items(items)
+        return self
+
+    def _windows_with_labels(self, items):
+        rows, win_of_row = [], []
+        for wi, (s, _, x0, y0, c) in enumerate(items):
+            polys, cls = self._window_labels(s, x0, y0, c)
+            if len(cls):
+                r = np.zeros(len(cls), dtype=A.LABEL_ROW_DTYPE)
+                r["poly"], r["cls"] = polys, cls
+                rows.append(r)
+                win_of_row.append(np.full(len(cls), wi, dtype=np.int32))
+        kept = np.zeros(len(items), dtype=bool)
+        if rows:
+            rows, win_of_row = np.concatenate(rows), np.concatenate(win_of_row)
+            table = A.upload_label_rows(rows, self.device)
+            iof = A.scene_label_rows(table, len(rows), win_of_row, [(x0, y0, c) for _, _, x0, y0, c in items], self.iof_thr, want_iof=True)
+            kept[win_of_row[iof.cpu().numpy() >= self.iof_thr]] = True      # (a zero-area label reports 0)
+        return kept
+
+    def _set_items(self, items):
+        self.items = list(items)
+        self.img_files = ["{}#{},{},{}".format(self.scene_files[s], x0, y0, c) for s, _, x0, y0, c in self.items]
+        self.label_files = [self.scene_label_files[s] for s, _, _, _, _ in self.items]
+
+    def set_arrays(self, images, polys, labels):
+        """Decoded scenes (uint8 HWC BGR) and their parsed labels (scene pixels) instead of files; plans the windows."""
+        self.img_files, self.label_files = [], []
+        super().set_arrays(images, polys, labels)
+        self.scene_files, self.scene_label_files = list(self.img_files), list(self.img_files)
+        self.plan_windows()
+
+    def shard(self, rank, world_size, pad=None):
+        """BaseDataset.shard over the ITEM table (same padding rules); the pool keeps holding whole scenes, filled on demand."""
+        self._set_items([self.items[i] for i in self._shard_indices(len(self.items), rank, world_size, self.augment if pad is None else pad)])
+        return self
+
+    # ------------------------------------------------------------------ the first stage of assemble_batch, through the window
+    def _use_shape(self, index, row):
+        s, _, x0, y0, c = self.items[index]
+        if self.jitter:
+            H, W = self._pool.shapes[s]
+            x0, y0 = jitter_window(self._wrng, H, W, c, self.scene_labels(s)[0], self.p_object)
+        if row != len(self.last_windows):
+            raise RuntimeError("SceneDataset: resize table and window table out of step")
+        self.last_windows.append((index, s, x0, y0, c))
+        return c, c
+
+    def _use_labels(self, index, row):
+        _, s, x0, y0, c = self.last_windows[row]
+        polys, cls = self._window_labels(s, x0, y0, c)
+        self._row_wins.append(np.full(len(cls), row, dtype=np.int32))
+        return polys, cls
+
+    def _pixel_stage(self, pool, items, luts):
+        pool.ensure(w[1] for w in self.last_windows)
+        return A.resize_hsv_windows(pool, [(s, (x0, y0, c), hw, interp, lut) for (_, s, x0, y0, c), (_, hw, interp, lut) in zip(self.last_windows, items)],
+                                    luts)
+
+    def _label_table(self, rows):
+        table = super()._label_table(rows)
+        A.scene_label_rows(table, len(rows), np.concatenate(self._row_wins), [w[2:] for w in self.last_windows], self.iof_thr)
+        return table
+
+    def assemble_batch(self, indices):
+        self.last_windows, self._row_wins = [], []
+        return super().assemble_batch(indices)
+
+
+class DOTASceneDataset(SceneDataset):
+    """Full-size DOTA scenes in DOTADataset's layout: `images/*.png` with `annfiles/*.txt` (datasets/DOTA_dataset.py)."""
+
+    def __init__(self, data_dir, class_names, hyp, augment, img_size, csl, normalized_labels=False, **kw):
+        super().__init__(hyp, img_size, augment, csl, normalized_labels, **kw)
+        self.scene_files = sorted(glob.glob(os.path.join(data_dir, "images", "*.png")))
+        self.scene_label_files = [p.replace("images", "annfiles").replace(".png", ".txt") for p in self.scene_files]
+        self.category = {name.replace(" ", "-"): i for i, name in enumerate(class_names)}
+        self.plan_windows()
+
+    load_files = DOTADataset.load_files

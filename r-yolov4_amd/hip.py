@@ -55,6 +55,9 @@ _SIGNATURES = {
     "ryolo_tile_mark": [_P, _P, _P, _P, _I, _L, _L, _P, _P],
     "ryolo_tile_emit": [_P, _P, _P, _L, _P, _P],
     "ryolo_nms_owner": [_P, _I, _L, _P, _Z, _P, _L, _P, _P, _P],
+    "ryolo_window_item_bytes": [ctypes.POINTER(_I)],
+    "ryolo_resize_hsv_windows": [_P, _P, _I, _L, _P, _P, _P],
+    "ryolo_scene_label_rows": [_P, _L, _P, _P, _I, ctypes.c_double, _P, _P],
     "ryolo_tile_fuse": [_P, _P, _P, _P, _P, _P, _I, _L, _L, _L, _I, _I, _P, _P, _P],
 }
 _lib = None

@@ -6,9 +6,14 @@ the reference either and raises NotImplementedError here.
 
 Device-side extras (keyword only, all optional): `device`, `imread`, `imsize`, `pool_budget_bytes` / `pool_slab_bytes` (HBM budget of the
 decoded-image pool, LRU beyond it), `decode_workers`, `side_stream` (assemble on a stream of the loader's own: the next batch is prepared
-under the current training step), `rank` / `world_size` (data parallel: each rank iterates and pools its shard of the files)."""
+under the current training step), `rank` / `world_size` (data parallel: each rank iterates and pools its shard of the files).
+
+`dataset_type="DOTA_scenes"` (this project's, not the reference's): `data_dir` holds FULL-SIZE scenes in the DOTA layout and the windows
+are cut on the device (datasets/scene_dataset.py); its keywords `overlap`, `rates`, `iof_thr`, `keep_empty`, `jitter`, `p_object`,
+`window_seed` pass through."""
 from ..datasets.base_dataset import DeviceLoader
 from ..datasets.DOTA_dataset import DOTADataset
+from ..datasets.scene_dataset import DOTASceneDataset
 from ..datasets.UCASAOD_dataset import UCASAODDataset
 
 
@@ -18,6 +23,8 @@ def load_data(data_dir, class_names, dataset_type, hyp, csl, img_size=608, batch
         dataset = UCASAODDataset(data_dir, class_names, hyp, img_size=img_size, augment=augment, csl=csl, **device_kw)
     elif dataset_type == "DOTA":
         dataset = DOTADataset(data_dir, class_names, hyp, img_size=img_size, augment=augment, csl=csl, **device_kw)
+    elif dataset_type == "DOTA_scenes":
+        dataset = DOTASceneDataset(data_dir, class_names, hyp, img_size=img_size, augment=augment, csl=csl, **device_kw)
     else:
         raise NotImplementedError
     return dataset, DeviceLoader(dataset, batch_size, shuffle, side_stream=side_stream, rank=rank, world_size=world_size)
