@@ -88,6 +88,32 @@ int ryolo_ap_per_class(const unsigned char* tp, const float* conf, const float* 
                        int nc, int niou, const double* recall_grid, const double* conf_grid, int nconf, void* workspace, size_t workspace_bytes,
                        double* ap, double* prec_at, double* rec_at, int64_t* n_labels, int64_t* n_pred, ryolo_stream_t stream);
 
+/* The matching of `get_batch_statistics` (test.py:130-145) for ONE full scene — thousands of detections and labels — spread over the
+ * chip, its rows appended to device-side accumulators; nothing is read back (lib/scene_eval.py).
+ * dets [max_det,7] = (x, y, w, h, theta_rad, score, cls), score descending (TiledDetector.run_async's `out`); num [1] its count on the
+ * device, clamped to [0, max_det]; rows >= *num are never read.  dets is only read: theta goes to degrees in registers.
+ * labels [nl,6] = (cls, x, y, w, h, theta_rad) GROUPED BY CLASS ascending, the caller's order kept inside a class; cls_off [nc+1] int32
+ * (device): class c owns rows [cls_off[c], cls_off[c+1]).  nl == 0 is legal (labels may be NULL).  nc <= 256, niou <= 16
+ * (RYOLO_ERR_UNSUPPORTED beyond); iouv [niou] ascending (device).
+ * Rule.  best(i) = the label of detection i's own class with the largest IoU (theta of both as theta / 3.14159274f * 180.f, the pair
+ * function of the NMS); a detection whose class is not an integer in [0, nc) (NaN included), or whose class has no label, has none.
+ *   owner(t) = the SMALLEST detection index i with best(i) == t and IoU(i, t) > iouv[0]
+ *   tp[i][k] = owner(best(i)) == i  &&  IoU(i, best(i)) > iouv[k]
+ * This is the reference's walk in score order: a candidate is a true positive iff its best label is not yet claimed, and one whose best
+ * label is taken stays a false positive — it never falls back to the second best — so who gets a label does not depend on the walk.
+ * Ties.  Equal IoU: the first label in the caller's order inside the class (what torch.max returns).  Equal score: detections keep
+ * their row order, i.e. the smaller row claims first.  IoU exactly equal to a threshold is not above it.
+ * Accumulators (cap rows): tp [cap][niou] bytes, conf [cap] = score, pcls [cap] = cls; cursor [1] int64 and overflow [1] int32 on the
+ * device, zeroed by the caller before the first scene.  With n = min(*num, max_det) and cur = *cursor the rows cur .. cur + n - 1 are
+ * written and the cursor advances by n; if cur + n > cap nothing is written, the cursor stays and *overflow = 1.
+ * Launches: label prologue + owner reset, one wave per detection (best label, one atomicMin on owner), a thread per detection (rows), the
+ * cursor.  Deterministic.  Every index that comes from data (cls_off entries, the class, *num, the stored best label) is clamped or
+ * checked before it addresses memory: a bad table gives wrong numbers, not a fault. */
+int ryolo_scene_match_workspace_bytes(int64_t max_det, int64_t nl, size_t* bytes);
+int ryolo_scene_match(const float* dets, const int32_t* num, int64_t max_det, const float* labels, const int32_t* cls_off, int64_t nl, int nc,
+                      const float* iouv, int niou, unsigned char* tp, float* conf, float* pcls, int64_t cap, int64_t* cursor, int32_t* overflow,
+                      void* workspace, size_t workspace_bytes, ryolo_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * YoloLayer — replaces model/yololayer.py:15-56 (YoloCSLLayer.forward) and :66-105 (YoloKFIoULayer.forward).
  * ------------------------------------------------------------------------------------------------------------ */

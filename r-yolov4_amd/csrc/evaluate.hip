@@ -338,3 +338,144 @@ extern "C" int ryolo_ap_per_class(const unsigned char* tp, const float* conf, co
     RY_CHECK_LAUNCH();
     return RY_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ full-scene matching
+// The same rule as map_match_kernel for ONE scene of thousands of detections and labels, spread over the chip.  The reference never falls
+// back to a second-best label, so the outcome per label does not depend on the walk: the owner of label t is the SMALLEST detection index
+// i (score order) whose best label of its own class is t with IoU > iouv[0], and detection i is a true positive at threshold k iff it
+// owns its best label and that IoU > iouv[k].  One wave per detection finds the best label among the prepared labels of its class and
+// claims it with one atomicMin; a thread per detection then writes its row behind a device-side cursor.  No serial phase, no host read.
+#define SM_WAVES 4
+
+static inline size_t sm_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+__device__ __forceinline__ int sm_count(const int32_t* __restrict__ num, int64_t max_det)
+{
+    const int64_t n = *num;
+    return (int)(n < 0 ? 0 : (n > max_det ? max_det : n));
+}
+
+__global__ __launch_bounds__(256) void scene_prep_kernel(const float* __restrict__ labels, int64_t nl, BoxPrep* __restrict__ prep,
+                                                         int32_t* __restrict__ owner)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nl) return;
+    const float PI_F = 3.14159274f;
+    const float* tr = labels + t * 6;
+    const float tb[5] = {tr[1], tr[2], tr[3], tr[4], tr[5] / PI_F * 180.f};
+    BoxPrep T;
+    box_prep(tb, T);
+    prep[t] = T;
+    owner[t] = INT_MAX;
+}
+
+__global__ __launch_bounds__(64 * SM_WAVES) void scene_best_kernel(const float* __restrict__ dets, const int32_t* __restrict__ num, int64_t max_det,
+                                                                   const BoxPrep* __restrict__ prep, const int32_t* __restrict__ cls_off, int64_t nl,
+                                                                   int nc, const float* __restrict__ iouv, float* __restrict__ best_iou,
+                                                                   int32_t* __restrict__ best_t, int32_t* __restrict__ owner)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * SM_WAVES + (threadIdx.x >> 6);
+    if (i >= sm_count(num, max_det)) return;                          // wave-uniform
+    const float* pr = dets + i * 7;
+    const float PI_F = 3.14159274f;
+    const float pb[5] = {pr[0], pr[1], pr[2], pr[3], pr[4] / PI_F * 180.f};   // degrees in registers: dets is never written
+    const float cls = pr[6];
+    int64_t lo = 0, hi = 0;
+    if (cls >= 0.f && cls < (float)nc) {                              // NaN fails both
+        const int c = (int)cls;
+        if ((float)c == cls && c >= 0 && c < nc) {
+            lo = cls_off[c];
+            hi = cls_off[c + 1];
+            lo = lo < 0 ? 0 : (lo > nl ? nl : lo);                    // a bad table gives wrong numbers, never an access outside prep
+            hi = hi < lo ? lo : (hi > nl ? nl : hi);
+        }
+    }
+    float bi = -1.f;
+    int bt = -1;
+    if (lo < hi) {
+        BoxPrep P;
+        box_prep(pb, P);
+        for (int64_t t = lo + lane; t < hi; t += 64) {
+            const BoxPrep T = prep[t];
+            const float v = boxes_far_apart(P, T) ? 0.f : rotated_iou_pair(P, T);
+            if (v > bi) { bi = v; bt = (int)t; }
+        }
+    }
+    // first maximum in label order: larger IoU wins, equal IoU the smaller label index, -1 (no label seen) loses to any index
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float oi = __shfl_xor(bi, o, 64);
+        const int ot = __shfl_xor(bt, o, 64);
+        if (ot >= 0 && (bt < 0 || oi > bi || (oi == bi && ot < bt))) { bi = oi; bt = ot; }
+    }
+    if (lane == 0) {
+        best_iou[i] = bi;
+        best_t[i] = bt;
+        if (bt >= 0 && bt < nl && bi > iouv[0]) atomicMin(&owner[bt], (int)i);
+    }
+}
+
+__global__ __launch_bounds__(256) void scene_emit_kernel(const float* __restrict__ dets, const int32_t* __restrict__ num, int64_t max_det, int64_t nl,
+                                                         const float* __restrict__ iouv, int niou, const float* __restrict__ best_iou,
+                                                         const int32_t* __restrict__ best_t, const int32_t* __restrict__ owner,
+                                                         unsigned char* __restrict__ tp, float* __restrict__ conf, float* __restrict__ pcls,
+                                                         int64_t cap, const int64_t* __restrict__ cursor)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t n = sm_count(num, max_det);
+    if (i >= n) return;
+    const int64_t cur = *cursor;
+    if (cur < 0 || cur > cap || n > cap - cur) return;               // overflow: nothing is written (scene_advance_kernel raises the flag)
+    const int bt = best_t[i];
+    const float bi = best_iou[i];
+    const bool hit = bt >= 0 && bt < nl && bi > iouv[0] && owner[bt] == (int)i;
+    unsigned char* row = tp + (cur + i) * niou;
+    for (int k = 0; k < niou; k++) row[k] = hit && bi > iouv[k] ? 1 : 0;
+    conf[cur + i] = dets[i * 7 + 5];
+    pcls[cur + i] = dets[i * 7 + 6];
+}
+
+// stream-ordered after every row is written and every read of the cursor
+__global__ void scene_advance_kernel(const int32_t* __restrict__ num, int64_t max_det, int64_t cap, int64_t* __restrict__ cursor,
+                                     int32_t* __restrict__ overflow)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const int64_t n = sm_count(num, max_det), cur = *cursor;
+    if (cur < 0 || cur > cap || n > cap - cur) *overflow = 1;
+    else *cursor = cur + n;
+}
+
+extern "C" int ryolo_scene_match_workspace_bytes(int64_t max_det, int64_t nl, size_t* bytes)
+{
+    if (!bytes || max_det < 0 || nl < 0) return RY_ERR_ARG;
+    *bytes = sm_align((size_t)nl * sizeof(BoxPrep)) + sm_align((size_t)nl * 4) + sm_align((size_t)max_det * 4) + sm_align((size_t)max_det * 4) + 256;
+    return RY_OK;
+}
+
+extern "C" int ryolo_scene_match(const float* dets, const int32_t* num, int64_t max_det, const float* labels, const int32_t* cls_off, int64_t nl,
+                                 int nc, const float* iouv, int niou, unsigned char* tp, float* conf, float* pcls, int64_t cap, int64_t* cursor,
+                                 int32_t* overflow, void* ws, size_t ws_bytes, hipStream_t stream)
+{
+    if (max_det < 0 || nl < 0 || nc < 1 || niou < 1 || cap < 0) return RY_ERR_ARG;
+    if (nc > MAP_MAX_CLASSES || niou > AP_MAX_T || max_det >= INT_MAX || nl >= INT_MAX) return RY_ERR_UNSUPPORTED;
+    if (max_det == 0) return RY_OK;
+    if (!dets || !num || !cls_off || !iouv || !tp || !conf || !pcls || !cursor || !overflow || !ws || (nl > 0 && !labels)) return RY_ERR_ARG;
+    size_t need = 0;
+    ryolo_scene_match_workspace_bytes(max_det, nl, &need);
+    if (ws_bytes < need) return RY_ERR_WORKSPACE;
+    unsigned char* base = reinterpret_cast<unsigned char*>(ws);
+    BoxPrep* prep = reinterpret_cast<BoxPrep*>(base);       base += sm_align((size_t)nl * sizeof(BoxPrep));
+    int32_t* owner = reinterpret_cast<int32_t*>(base);      base += sm_align((size_t)nl * 4);
+    float* best_iou = reinterpret_cast<float*>(base);       base += sm_align((size_t)max_det * 4);
+    int32_t* best_t = reinterpret_cast<int32_t*>(base);
+    if (nl > 0)
+        hipLaunchKernelGGL(scene_prep_kernel, dim3((unsigned)ry_cdiv(nl, 256)), dim3(256), 0, stream, labels, nl, prep, owner);
+    hipLaunchKernelGGL(scene_best_kernel, dim3((unsigned)ry_cdiv(max_det, SM_WAVES)), dim3(64 * SM_WAVES), 0, stream, dets, num, max_det, prep, cls_off,
+                       nl, nc, iouv, best_iou, best_t, owner);
+    hipLaunchKernelGGL(scene_emit_kernel, dim3((unsigned)ry_cdiv(max_det, 256)), dim3(256), 0, stream, dets, num, max_det, nl, iouv, niou, best_iou,
+                       best_t, owner, tp, conf, pcls, cap, cursor);
+    hipLaunchKernelGGL(scene_advance_kernel, dim3(1), dim3(64), 0, stream, num, max_det, cap, cursor, overflow);
+    RY_CHECK_LAUNCH();
+    return RY_OK;
+}

@@ -101,6 +101,10 @@ class ImagePool:
         k, off = self._where[i]
         return self._slabs[k].data_ptr() - self.buf.data_ptr() + off
 
+    def host_image(self, i):
+        """Image i as its decoder returns it (uint8 HWC BGR on the host); residency is not touched."""
+        return self._decode(int(i))
+
     def resident_bytes(self):
         return self._resident
 

@@ -10,6 +10,7 @@ NMS — the workflow users of the reference rebuild by hand around detect.py, wh
     TiledDetector(..., fuse="box" | "wbf")                                          kept boxes absorb the boxes they suppressed (FUSE)
     TiledDetector.run_async(scene) -> (out [max_det, 7], num [1] int32)             the same with the count left on the device
     TiledDetector.detect_files(paths) -> iterator of (path, Tensor[n, 7])           scene i + 1 decoded / uploaded while scene i runs
+    TiledDetector.iter_async(paths) -> iterator of (path, out, num)                 the same with the counts left on the device (lib/scene_eval.py)
     write_dota_task1({name: dets}, out_dir, class_names)                            DOTA Task1 files (Task1_<class>.txt)
 
 Device side (csrc/tiled.hip): per group ryolo_tile_cut (scene -> the graph's static input), the graph replay, ryolo_tile_collect (scene
@@ -396,6 +397,43 @@ class TiledDetector:
             if not overlap and i + 1 < len(paths):
                 nxt = load(paths[i + 1])
             yield path, res
+
+    def iter_async(self, paths, imread=None, overlap=True):
+        """detect_files without the count read: iterate (path, out [max_det, 7], num [1] int32), both on the device and owned by the
+        detector as run_async returns them — valid until the consumer asks for the next scene, and whatever it launches on them must go
+        to the current stream.  Nothing is read back and nothing waits for the device.  overlap=True: scene i + 1 is decoded and uploaded
+        on a side stream while scene i runs; its memory is released to that stream only behind an event recorded after scene i's
+        launches, since no host read says that they are done."""
+        from ..datasets.base_dataset import _default_imread
+        imread = imread or _default_imread
+        paths = list(paths)
+        main = torch.cuda.current_stream(self.device)
+        if overlap and self._side is None:
+            self._side = torch.cuda.Stream(device=self.device)
+
+        def load(path):
+            if not overlap:
+                return self._place(imread(path)), None
+            with torch.cuda.stream(self._side):
+                placed = self._place(imread(path))
+                return placed, self._side.record_event()
+
+        nxt = load(paths[0]) if paths else None
+        for i, path in enumerate(paths):
+            placed, ev = nxt
+            if ev is not None:
+                main.wait_event(ev)
+            out, num = self._enqueue(placed)
+            if overlap:
+                done = main.record_event()
+                nxt = load(paths[i + 1]) if i + 1 < len(paths) else None
+                self._side.wait_event(done)   # a later upload may take scene i's memory: it starts after scene i's launches
+            else:
+                self._last = placed           # one stream: reuse is ordered by it (run_async's rule)
+            del placed
+            yield path, out, num
+            if not overlap and i + 1 < len(paths):
+                nxt = load(paths[i + 1])
 
 
 # ------------------------------------------------------------------------------------------ DOTA Task1 output
