@@ -377,20 +377,12 @@ int ryolo_dets_to_polys(float* dets, const int* img_of_det, const int* shapes, i
  * Full-scene (tiled) detection (csrc/tiled.hip; lib/tiled.py).  The reference detects on offline-cut patches only (data/DOTA.yaml,
  * detect.py letterboxes a whole file to img_size); these stages cut a scene into overlapping windows, feed them group by group to the
  * captured forward + post_process, and merge the per-window detections in scene coordinates with class-wise rotated NMS on the device.
- * A scene of T windows in groups of B: T_pad = ceil(T / B) * B, candidate slot of detection j of window w = w * mk + j, ld = T_pad * mk.
+ * A scene of T entries (an entry is a window seen through a view, below) in groups of B: T_pad = ceil(T / B) * B, candidate slot of
+ * detection j of entry e = e * mk + j, ld = T_pad * mk.
  * ------------------------------------------------------------------------------------------------------------ */
-/* windows win0 .. win0 + count - 1 of the table win int64 [nwin][5] = (byte offset of the window's source image from pool, its height,
- * width, window origin x0, y0) -> dst fp32 [>= count, 3, S, S] slots 0 .. count - 1 as RGB / 255 (114 / 255 outside the source image);
- * later slots are not touched.  S % 4 == 0.  Bit-identical to ryolo_paste_rects(fill = 114) + ryolo_to_tensor. */
-int ryolo_tile_cut(const uint8_t* pool, const int64_t* win, int64_t win0, int count, int S, float* dst, ryolo_stream_t stream);
-/* one group's post_process output dets [batch, mk, 7] / num [batch] (windows win0 .. win0 + batch - 1 of a scene of nwin windows;
- * geom fp32 [nwin][3] = (x0, y0, rate)) -> cand [ld][7] rows (x + x0) / rate, (y + y0) / rate, w / rate, h / rate, theta, score, cls
- * at slot (win0 + b) * mk + j, key [nc][ld] = score in the row of the class, -inf in the others, fkey [ld] = -inf.  Slots past num[b]
- * and windows at or past nwin: zero rows, -inf keys.  (win0 + batch) * mk <= ld. */
-int ryolo_tile_collect(const float* dets, const int32_t* num, int batch, int64_t mk, const float* geom, int64_t win0, int64_t nwin, int nc,
-                       int64_t ld, float* cand, float* key, float* fkey, ryolo_stream_t stream);
-/* Flip / 90-degree views of a window (test-time orientation ensembling; lib/tiled.py VIEWS).  With win the S x S x 3 window
- * ryolo_tile_cut sees (114 outside the scene: the fill turns with the window) and continuous coordinates (pixel i covers [i, i + 1)):
+/* Every window is cut, and its detections are collected, through one of the eight flip / 90-degree views (test-time orientation
+ * ensembling; lib/tiled.py VIEWS; plain detection is view id), and the tables have one row per entry.  With win the S x S x 3 window
+ * at the entry's origin (114 outside the scene: the fill turns with the window) and continuous coordinates (pixel i covers [i, i + 1)):
  *   code  name           pixels (numpy)                        view point (x, y) -> window point   theta' before the wrap
  *   0     id             win                                   (x, y)                              theta (bits unchanged)
  *   1     hflip          win[:, ::-1]                          (S - x, y)                          -theta
@@ -404,16 +396,20 @@ int ryolo_tile_collect(const float* dets, const int32_t* num, int batch, int64_t
  * two selects (lib/general.py:14-15): >= pi/2 -> subtract pi, then < -pi/2 -> add pi; fp32 with (float)pi/2 and (float)pi, one
  * operation per step.
  *
- * ryolo_tile_cut with the window table win int64 [nwin][6] = (ryolo_tile_cut's five columns, view code): slot k of dst holds view
- * `code` of window win0 + k as RGB / 255.  Same contract otherwise (pool + byte offset at any alignment, S % 4 == 0, slots >= count are
- * not touched, no intermediate canvas).  Codes 0-3 are index arithmetic (a reversed row is read forward and reversed in registers);
- * codes 4-7 turn 32 x 32 pixel tiles through LDS.  The table lives on the device and the call does not read it back: a row whose code
- * is outside 0-7 leaves its slot untouched (lib/tiled.py validates the names it encodes). */
+ * The cut: entries win0 .. win0 + count - 1 of the table win int64 [nwin][6] = (byte offset of the entry's source image from pool (any
+ * alignment), its height, width, window origin x0, y0, view code) -> dst fp32 [>= count, 3, S, S]: slot k holds view `code` of the
+ * window of entry win0 + k as RGB / 255 (114 / 255 outside the source image); slots >= count are not touched.  S % 4 == 0.  No
+ * intermediate canvas; for code 0 bit-identical to ryolo_paste_rects(fill = 114) + ryolo_to_tensor.  Codes 0-3 are index arithmetic
+ * (a reversed row is read forward and reversed in registers); codes 4-7 turn 32 x 32 pixel tiles through LDS.  The table lives on the
+ * device and the call does not read it back: a row whose code is outside 0-7 leaves its slot untouched (lib/tiled.py validates the
+ * names it encodes). */
 int ryolo_tile_cut_views(const uint8_t* pool, const int64_t* win, int64_t win0, int count, int S, float* dst, ryolo_stream_t stream);
-/* ryolo_tile_collect for entries seen through a view: geom fp32 [nwin][4] = (x0, y0, rate, view code), S the window size.  The row
- * of a detection (x, y, w, h, theta, score, cls) is mapped to its window point and theta' by the table above, then shifted as
- * ryolo_tile_collect does: ((px + x0) / rate, (py + y0) / rate, w / rate, h / rate, theta', score, cls).  Every slot of the group is
- * written exactly once (an entry whose code is outside 0-7 as empty slots); no atomics, deterministic. */
+/* The collect: one group's post_process output dets [batch, mk, 7] / num [batch] (entries win0 .. win0 + batch - 1 of a scene of nwin
+ * entries; geom fp32 [nwin][4] = (x0, y0, rate, view code), S the window size).  The row of a detection (x, y, w, h, theta, score, cls)
+ * is mapped to its window point (px, py) and theta' by the table above, then shifted to scene pixels: cand [ld][7] row
+ * ((px + x0) / rate, (py + y0) / rate, w / rate, h / rate, theta', score, cls) at slot (win0 + b) * mk + j, key [nc][ld] = score in the
+ * row of the class, -inf in the others, fkey [ld] = -inf.  Slots past num[b], entries at or past nwin and entries whose code is outside
+ * 0-7: zero rows, -inf keys.  Every slot of the group is written exactly once; no atomics, deterministic.  (win0 + batch) * mk <= ld. */
 int ryolo_tile_collect_views(const float* dets, const int32_t* num, int batch, int64_t mk, const float* geom, int64_t win0, int64_t nwin,
                              int nc, int64_t ld, int S, float* cand, float* key, float* fkey, ryolo_stream_t stream);
 /* skey / order [nc, K] = ryolo_topk_desc of key -> rboxes [nc, K, 5] = (x, y, w, h, theta degrees) of the selected candidates in scene

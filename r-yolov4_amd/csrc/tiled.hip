@@ -2,15 +2,15 @@
 // windows goes through the captured forward + post_process (Yolo.capture_inference(..., post=...)), and the per-window detections are
 // merged back in scene coordinates with CLASS-WISE rotated NMS — all on the device, no host read between groups (lib/tiled.py).
 //
-//   tile_cut_kernel      uint8 HWC BGR scene (pool base + byte offset) -> the graph's static input fp32 [B,3,S,S] as RGB / 255, 114 / 255
-//                        outside the scene; one launch per window group.  Bit-identical to ryolo_paste_rects(fill=114) + ryolo_to_tensor
-//                        (the chain it replaces) without their intermediate canvas.
-//   tile_cut_views_kernel  the same cut with the window written in one of the eight flip / 90-degree views (view code per table row); the
-//                        four transposing views turn a 32 x 32 pixel tile through LDS.
-//   tile_collect_kernel  dets [B,mk,7] / num [B] of a group -> candidate rows in scene coordinates at the fixed slot window * mk + j and the
-//                        per-class key rows key [nc][ld] (score in the row of the box's class, -inf elsewhere); every slot of the group is
-//                        written exactly once (no fill pass, no atomics: deterministic).
-//   tile_collect_views_kernel  the same with the view's inverse map (point and angle) in front of the shift.
+//   tile_cut_views_kernel  uint8 HWC BGR scene (pool base + byte offset) -> the graph's static input fp32 [B,3,S,S] as RGB / 255, 114 / 255
+//                        outside the scene, every window written in one of the eight flip / 90-degree views (view code per table row;
+//                        the four transposing views turn a 32 x 32 pixel tile through LDS); one launch per group of entries.  View id is
+//                        bit-identical to ryolo_paste_rects(fill=114) + ryolo_to_tensor (the chain it replaces) without their
+//                        intermediate canvas.
+//   tile_collect_views_kernel  dets [B,mk,7] / num [B] of a group -> candidate rows in scene coordinates (the view's inverse map of point
+//                        and angle, then the shift) at the fixed slot entry * mk + j and the per-class key rows key [nc][ld] (score in
+//                        the row of the box's class, -inf elsewhere); every slot of the group is written exactly once (no fill pass, no
+//                        atomics: deterministic).
 //   (ryolo_topk_desc over the nc key rows)
 //   tile_gather_kernel   per-class top-K slots -> NMS boxes [nc,K,5] in scene pixels, theta in degrees, NO class offset: the per-image path
 //                        separates classes by cls * 4096 px (lib/general.py:14), which collides on scenes wider than 4096 px; here a
@@ -22,78 +22,6 @@
 //   tile_emit_kernel     out [max_det,7] = candidate (or fused) rows in that order, zero padded.
 // Compiled with -ffp-contract=off: the coordinate mapping (x + x0) / rate is restated bit for bit by numpy in the tests.
 #include "common.h"
-
-// window table rows (int64 [nwin][5]): byte offset of the window's source image from `pool`, its height, width, window origin x0, y0
-#define TW_ROW 5
-
-// One thread = 4 consecutive output pixels of one window row (S % 4 == 0): 12 source bytes, one float4 per colour plane.
-__global__ __launch_bounds__(256) void tile_cut_kernel(const uint8_t* __restrict__ pool, const int64_t* __restrict__ win, int S,
-                                                       float* __restrict__ dst)
-{
-    const int w = blockIdx.y;
-    const int sq = S >> 2;
-    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (q >= (int64_t)S * sq) return;
-    const int y = (int)(q / sq);
-    const int x = (int)(q - (int64_t)y * sq) * 4;
-    const int64_t* t = win + (int64_t)w * TW_ROW;
-    const int64_t off = t[0];
-    const int H = (int)t[1], W = (int)t[2];
-    const int sy = (int)t[4] + y, sx = (int)t[3] + x;
-    uint8_t px[12];
-    if (sy < H && sx + 4 <= W) {
-        __builtin_memcpy(px, pool + off + ((int64_t)sy * W + sx) * 3, 12);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            px[3 * k] = px[3 * k + 1] = px[3 * k + 2] = (uint8_t)114;
-            if (sy < H && sx + k < W) {
-                const uint8_t* sp = pool + off + ((int64_t)sy * W + sx + k) * 3;
-                px[3 * k] = sp[0]; px[3 * k + 1] = sp[1]; px[3 * k + 2] = sp[2];
-            }
-        }
-    }
-    const int64_t plane = (int64_t)S * S;
-    float* o = dst + (int64_t)w * 3 * plane + (int64_t)y * S + x;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {                                       // BGR -> RGB, .float() / 255 (ryolo_to_tensor's expression)
-        float v[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) v[k] = (float)px[k * 3 + (2 - c)] / 255.0f;
-        *reinterpret_cast<float4*>(o + c * plane) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-}
-
-// One thread = one detection slot j of window b of the group (global window win0 + b).
-__global__ __launch_bounds__(256) void tile_collect_kernel(const float* __restrict__ dets, const int32_t* __restrict__ num, int64_t mk,
-                                                           const float* __restrict__ geom, int64_t win0, int64_t nwin, int nc, int64_t ld,
-                                                           float* __restrict__ cand, float* __restrict__ key, float* __restrict__ fkey)
-{
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int b = blockIdx.y;
-    if (j >= mk) return;
-    const int64_t wg = win0 + b;
-    const int64_t slot = wg * mk + j;
-    float* c = cand + slot * 7;
-    float s = -INFINITY;
-    int cls = -1;
-    if (wg < nwin && j < (int64_t)num[b]) {
-        const float* d = dets + ((int64_t)b * mk + j) * 7;
-        const float* g = geom + wg * 3;
-        const float x0 = g[0], y0 = g[1], rate = g[2];
-        c[0] = (d[0] + x0) / rate;
-        c[1] = (d[1] + y0) / rate;
-        c[2] = d[2] / rate;
-        c[3] = d[3] / rate;
-        c[4] = d[4]; c[5] = d[5]; c[6] = d[6];
-        s = d[5];
-        cls = (int)d[6];
-    } else {
-        for (int t = 0; t < 7; t++) c[t] = 0.f;
-    }
-    for (int k = 0; k < nc; k++) key[(int64_t)k * ld + slot] = k == cls ? s : -INFINITY;
-    fkey[slot] = -INFINITY;
-}
 
 __global__ __launch_bounds__(256) void tile_gather_kernel(const float* __restrict__ cand, const float* __restrict__ skey,
                                                           const int64_t* __restrict__ order, int64_t K, float* __restrict__ rboxes)
@@ -233,18 +161,19 @@ __global__ __launch_bounds__(256) void tile_emit_kernel(const float* __restrict_
     }
 }
 
-// ------------------------------------------------------------------------------------------ flip / 90-degree views
+// ------------------------------------------------------------------------------------------ cut and collect, in a flip / 90-degree view
 // View codes (include/ryolo.h): 0 id, 1 hflip, 2 vflip, 3 rot180, 4 transpose, 5 rot90, 6 rot270, 7 antitranspose.  With `win` the
-// S x S window tile_cut_kernel produces (114 outside the scene: the fill turns with the window), view pixel (y, x) is
+// S x S window at the entry's origin (114 outside the scene: the fill turns with the window), view pixel (y, x) is
 //   codes 0-3:  win[fy ? S-1-y : y][fx ? S-1-x : x]     fx = code & 1, fy = code & 2
 //   codes 4-7:  win[fr ? S-1-x : x][fc ? S-1-y : y]     fc = code == 5 || code == 7, fr = code == 6 || code == 7
-// window table rows (int64 [nwin][6]): the five columns of TW_ROW and the view code
+// window table rows (int64 [nwin][6]): byte offset of the window's source image from `pool`, its height, width, window origin x0, y0,
+// view code
 #define TV_ROW 6
 #define TV_TILE 32
 #define TV_PITCH 33
 
 // 4 consecutive pixels of a window row as 12 BGR bytes packed in 3 dwords (byte n of the 12 = TV_BYTE(q, n)), 114 outside the H x W
-// source: tile_cut_kernel's read
+// source
 #define TV_BYTE(q, n) (((q)[(n) >> 2] >> (8 * ((n) & 3))) & 255u)
 __device__ __forceinline__ void tv_load4(const uint8_t* __restrict__ src, int H, int W, int sy, int sx, uint32_t* q)
 {
@@ -263,7 +192,8 @@ __device__ __forceinline__ void tv_load4(const uint8_t* __restrict__ src, int H,
 
 // One block = one window (blockIdx.y) and 256 threads x 4 output pixels; every thread reads 12 contiguous source bytes along a source
 // row and stores one float4 per colour plane along an output row, whatever the view.
-//   codes 0-3: tile_cut_kernel's linear mapping (a block = 1024 consecutive output pixels).  A reversed row is read forward from the
+//   codes 0-3: a linear mapping, one thread = 4 consecutive output pixels of one window row (a block = 1024 consecutive output
+//     pixels; blocks past S * S / 4 groups, which only S % 32 != 0 leaves, exit).  A reversed row is read forward from the
 //     mirrored column S - 4 - x (S % 4 == 0 keeps the 4-pixel groups aligned under the mirror) and reversed in registers.
 //   codes 4-7: a block turns the 32 x 32 pixel tile blockIdx.x = ty * ceil(S / 32) + tx through LDS, one dword (B | G << 8 | R << 16) per
 //     pixel at tile[i][j] (i = output x, j = output y inside the tile), row pitch TV_PITCH = 33 dwords.
@@ -337,7 +267,8 @@ __global__ __launch_bounds__(256) void tile_cut_views_kernel(const uint8_t* __re
     }
 }
 
-// tile_collect_kernel with the view's inverse map in front of the shift: geom rows (x0, y0, rate, view code), S the window size.  The
+// One thread = one detection slot j of entry b of the group (global entry win0 + b): the view's inverse map, then the shift to scene
+// pixels (x + x0) / rate.  geom rows (x0, y0, rate, view code), S the window size.  The
 // point map and the angle (fp32, one rounding per step; -theta is exact) follow include/ryolo.h; the six views that change theta wrap it
 // once through norm_angle's two selects (lib/general.py:14-15).  An entry with an unknown code is written as an empty slot.
 __global__ __launch_bounds__(256) void tile_collect_views_kernel(const float* __restrict__ dets, const int32_t* __restrict__ num, int64_t mk,
@@ -387,31 +318,6 @@ __global__ __launch_bounds__(256) void tile_collect_views_kernel(const float* __
     }
     for (int k = 0; k < nc; k++) key[(int64_t)k * ld + slot] = k == cls ? s : -INFINITY;
     fkey[slot] = -INFINITY;
-}
-
-extern "C" int ryolo_tile_cut(const uint8_t* pool, const int64_t* win, int64_t win0, int count, int S, float* dst, hipStream_t stream)
-{
-    if (count < 0 || win0 < 0 || S <= 0) return RY_ERR_ARG;
-    if (S % 4 != 0 || count > 65535) return RY_ERR_UNSUPPORTED;
-    if (count == 0) return RY_OK;
-    if (!pool || !win || !dst) return RY_ERR_ARG;
-    hipLaunchKernelGGL(tile_cut_kernel, dim3((unsigned)ry_cdiv((int64_t)S * (S / 4), 256), count), dim3(256), 0, stream, pool,
-                       win + win0 * TW_ROW, S, dst);
-    RY_CHECK_LAUNCH();
-    return RY_OK;
-}
-
-extern "C" int ryolo_tile_collect(const float* dets, const int32_t* num, int batch, int64_t mk, const float* geom, int64_t win0, int64_t nwin,
-                                  int nc, int64_t ld, float* cand, float* key, float* fkey, hipStream_t stream)
-{
-    if (batch < 0 || mk < 0 || win0 < 0 || nwin < 0 || nc < 0 || ld < 0) return RY_ERR_ARG;
-    if ((win0 + batch) * mk > ld || batch > 65535) return RY_ERR_ARG;      // every slot of the group lies inside the candidate rows
-    if (batch == 0 || mk == 0) return RY_OK;
-    if (!dets || !num || !geom || !cand || !fkey || (nc && !key)) return RY_ERR_ARG;
-    hipLaunchKernelGGL(tile_collect_kernel, dim3((unsigned)ry_cdiv(mk, 256), batch), dim3(256), 0, stream, dets, num, mk, geom, win0, nwin, nc,
-                       ld, cand, key, fkey);
-    RY_CHECK_LAUNCH();
-    return RY_OK;
 }
 
 extern "C" int ryolo_tile_cut_views(const uint8_t* pool, const int64_t* win, int64_t win0, int count, int S, float* dst, hipStream_t stream)

@@ -24,7 +24,7 @@ import numpy as np
 from . import augment as A
 from .base_dataset import BaseDataset
 from .DOTA_dataset import DOTADataset
-from ..lib.tiled import _starts
+from ..lib.tiled import axis_starts
 
 
 def scene_windows(H, W, size, overlap, rates=(1.0,)):
@@ -47,8 +47,8 @@ def scene_windows(H, W, size, overlap, rates=(1.0,)):
         stride = c - int(overlap / float(r) + 0.5)
         if c <= 0 or stride <= 0 or c >= A.WINDOW_COORD_MAX:
             raise ValueError(f"scene_windows: rate {r} gives a window of {c} pixels with stride {stride}")
-        xs = _starts(int(W), c, stride)
-        for y0 in _starts(int(H), c, stride):
+        xs = axis_starts(int(W), c, stride)
+        for y0 in axis_starts(int(H), c, stride):
             out.extend((ri, x0, y0, c) for x0 in xs)
     return out
 

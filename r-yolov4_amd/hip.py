@@ -49,8 +49,6 @@ _SIGNATURES = {
     "ryolo_encode_labels": [_P, _L, _I, _I, _P, _P, _I, _P, _P, _P, _P],
     "ryolo_polys_to_xywha": [_P, _L, _P, _P],
     "ryolo_dets_to_polys": [_P, _P, _P, _I, _I, _L, _P, _P],
-    "ryolo_tile_cut": [_P, _P, _L, _I, _I, _P, _P],
-    "ryolo_tile_collect": [_P, _P, _I, _L, _P, _L, _L, _I, _L, _P, _P, _P, _P],
     "ryolo_tile_cut_views": [_P, _P, _L, _I, _I, _P, _P],
     "ryolo_tile_collect_views": [_P, _P, _I, _L, _P, _L, _L, _I, _L, _I, _P, _P, _P, _P],
     "ryolo_tile_merge_gather": [_P, _P, _P, _I, _L, _P, _P],

@@ -13,17 +13,18 @@ NMS — the workflow users of the reference rebuild by hand around detect.py, wh
     TiledDetector.iter_async(paths) -> iterator of (path, out, num)                 the same with the counts left on the device (lib/scene_eval.py)
     write_dota_task1({name: dets}, out_dir, class_names)                            DOTA Task1 files (Task1_<class>.txt)
 
-Device side (csrc/tiled.hip): per group ryolo_tile_cut (scene -> the graph's static input), the graph replay, ryolo_tile_collect (scene
-rows at the fixed slot window * mk + j, per-class keys); then per scene ryolo_topk_desc over the nc class rows, ryolo_tile_merge_gather,
+Device side (csrc/tiled.hip): a scene's entries are windows x views, window-major (entry e = window_index * len(views) + view_index;
+with the default views=("id",) the entries are the windows).  Per group of `batch` entries ryolo_tile_cut_views (scene -> the graph's
+static input, every entry's window in its view), the graph replay, ryolo_tile_collect_views (the view's boxes back in the window, then
+scene rows at the fixed slot e * mk + j, per-class keys); then per scene ryolo_topk_desc over the nc class rows, ryolo_tile_merge_gather,
 ryolo_nms_rotated_batched with batch = nc (no cls * 4096 offset: post_process's class separation collides on scenes wider than 4096 px),
 ryolo_tile_mark, ryolo_topk_desc over the kept entries (score desc, slot asc) and ryolo_tile_emit.  No allocation and no host read after the
 scene's upload; __call__ reads one count per scene.
 
-Views (test-time orientation ensembling; an overhead scene has no preferred orientation): with views other than ("id",) a scene's entries
-are windows x views, window-major (entry e = window_index * len(views) + view_index), so the views of one window are cut back to back.
-ryolo_tile_cut_views writes an entry's window in its view (flips by index arithmetic, the transposing views through LDS) and
-ryolo_tile_collect_views maps the view's boxes back to the window (point, theta wrapped into [-pi/2, pi/2)) in front of the shift; the
-candidate slot is e * mk + j and the merge is unchanged: it keeps the best-scoring box of a cluster.
+Views (test-time orientation ensembling; an overhead scene has no preferred orientation): the views of one window are cut back to
+back.  The cut writes an entry's window in its view (flips by index arithmetic, the transposing views through LDS) and the collect maps
+the view's boxes back to the window (point, theta wrapped into [-pi/2, pi/2)) in front of the shift; "id" is the view that changes
+neither a pixel's place nor a bit of a box.  The merge does not know about views: it keeps the best-scoring box of a cluster.
 The definition of the eight views is in include/ryolo.h.
 
 Fusion (fuse="box" | "wbf", default None = the merge above, bit for bit): what makes the extra replays of rates x views pay beyond
@@ -81,7 +82,8 @@ def resized_extent(H, W, rate):
     return int(H * rate + 0.5), int(W * rate + 0.5)
 
 
-def _starts(L, size, stride):
+def axis_starts(L, size, stride):
+    """Window starts along an axis of length L (tile_plan states the rule)."""
     if L <= size:
         return [0]
     out, x = [], 0
@@ -112,8 +114,8 @@ def tile_plan(H, W, size, overlap, rates=(1.0,)):
         h, w = resized_extent(H, W, float(r))
         if h <= 0 or w <= 0:
             raise ValueError(f"tile_plan: rate {r} leaves nothing of a {H} x {W} scene")
-        xs = _starts(w, size, stride)
-        for y0 in _starts(h, size, stride):
+        xs = axis_starts(w, size, stride)
+        for y0 in axis_starts(h, size, stride):
             out.extend((ri, x0, y0) for x0 in xs)
     return out
 
@@ -137,8 +139,8 @@ class ScenePlan:
     """Static buffers of one (H, W, rates, views): entry table, candidate rows, class keys, merge and final-order buffers, resized copies.
     `det` supplies device, batch, mk (detection rows per window), nc, size, overlap, rates, max_nms and max_det (a TiledDetector) and
     optionally views (default ("id",)).  An entry is a window seen through a view: entries = windows x views, window-major; T counts
-    entries, and groups of `batch` entries share one replay.  With views == ("id",) entries are the windows and the tables are those of
-    ryolo_tile_cut / ryolo_tile_collect; otherwise they carry the view code for ryolo_tile_cut_views / ryolo_tile_collect_views."""
+    entries, and groups of `batch` entries share one replay.  The tables carry every entry's view code (its index in VIEWS, 0 for "id")
+    for ryolo_tile_cut_views / ryolo_tile_collect_views."""
 
     def __init__(self, det, H, W):
         dev, B, mk, nc, S = det.device, det.batch, det.mk, det.nc, det.size
@@ -146,7 +148,6 @@ class ScenePlan:
         self.batch, self.mk, self.nc, self.max_det = B, mk, nc, det.max_det
         self.size = S
         self.views = check_views(getattr(det, "views", ("id",)))
-        self.plain = self.views == ("id",)
         self.windows = tile_plan(H, W, S, det.overlap, det.rates)
         self.entries = tile_entries(H, W, S, det.overlap, det.rates, self.views)
         self.extents = [resized_extent(H, W, r) for r in det.rates]
@@ -157,16 +158,12 @@ class ScenePlan:
         wa = np.asarray([e[:3] for e in self.entries], dtype=np.int64).reshape(-1, 3)
         code = np.asarray([VIEWS.index(e[3]) for e in self.entries], dtype=np.int64)
         ext = np.asarray(self.extents, dtype=np.int64)
-        cols = [np.zeros(T, np.int64), ext[wa[:, 0], 0], ext[wa[:, 0], 1], wa[:, 1], wa[:, 2]]       # src_off set per scene
-        gcols = [wa[:, 1], wa[:, 2], np.asarray(det.rates, np.float32)[wa[:, 0]]]
-        if not self.plain:
-            cols.append(code)
-            gcols.append(code)
-        self.rows = np.stack(cols, 1)
+        # win rows (src_off, set per scene; source height, width; x0, y0; view code) and geom rows (x0, y0, rate, view code)
+        self.rows = np.stack([np.zeros(T, np.int64), ext[wa[:, 0], 0], ext[wa[:, 0], 1], wa[:, 1], wa[:, 2], code], 1)
         self.rate_of = wa[:, 0]
-        self.win = torch.empty(self.rows.shape, dtype=i64, device=dev)
-        self.geom = torch.empty((T, len(gcols)), dtype=f32, device=dev)
-        _h2d(self.geom, np.stack(gcols, 1).astype(np.float32))
+        self.win = torch.empty((T, 6), dtype=i64, device=dev)
+        self.geom = torch.empty((T, 4), dtype=f32, device=dev)
+        _h2d(self.geom, np.stack([wa[:, 1], wa[:, 2], np.asarray(det.rates, np.float32)[wa[:, 0]], code], 1).astype(np.float32))
         # resized copies of the scene (rates != 1), one staging buffer
         self.stage_off, total = [], 0
         for r, (h, w) in zip(det.rates, self.extents):
@@ -175,7 +172,7 @@ class ScenePlan:
                 total += ((h * w * 3 + 15) // 16) * 16
         self.stage = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
         self.resize_items = [(ri, h, w) for ri, (r, (h, w)) in enumerate(zip(det.rates, self.extents)) if r != 1.0]
-        # candidates and keys: every slot is written by ryolo_tile_collect / ryolo_tile_collect_views
+        # candidates and keys: every slot is written by ryolo_tile_collect_views
         self.cand = torch.empty((ld, 7), dtype=f32, device=dev)
         self.key = torch.empty((nc, ld), dtype=f32, device=dev)
         self.fkey = torch.empty(ld, dtype=f32, device=dev)
@@ -204,18 +201,13 @@ class ScenePlan:
     def cut(self, scene, g, dst):
         """Group g's entries of the scene at device address `scene` -> dst [batch, 3, size, size] (slots past the last entry untouched)."""
         e0 = g * self.batch
-        hip.call("ryolo_tile_cut" if self.plain else "ryolo_tile_cut_views", scene, hip.ptr(self.win), e0, min(self.batch, self.T - e0),
-                 self.size, hip.ptr(dst), hip.stream())
+        hip.call("ryolo_tile_cut_views", scene, hip.ptr(self.win), e0, min(self.batch, self.T - e0), self.size, hip.ptr(dst), hip.stream())
 
     def collect(self, dets, num, g):
         """Group g's post_process output dets [batch, mk, 7] / num [batch] -> candidate rows and class keys of its slots."""
         B = self.batch
-        if self.plain:
-            hip.call("ryolo_tile_collect", hip.ptr(dets), hip.ptr(num), B, self.mk, hip.ptr(self.geom), g * B, self.T, self.nc, self.ld,
-                     hip.ptr(self.cand), hip.ptr(self.key), hip.ptr(self.fkey), hip.stream())
-        else:
-            hip.call("ryolo_tile_collect_views", hip.ptr(dets), hip.ptr(num), B, self.mk, hip.ptr(self.geom), g * B, self.T, self.nc,
-                     self.ld, self.size, hip.ptr(self.cand), hip.ptr(self.key), hip.ptr(self.fkey), hip.stream())
+        hip.call("ryolo_tile_collect_views", hip.ptr(dets), hip.ptr(num), B, self.mk, hip.ptr(self.geom), g * B, self.T, self.nc, self.ld,
+                 self.size, hip.ptr(self.cand), hip.ptr(self.key), hip.ptr(self.fkey), hip.stream())
 
     def merge(self, merge_iou, gt_only=True, fuse=None):
         """Class-wise rotated NMS over every collected candidate, then the final order -> (out [max_det, 7], num [1]) on the device.
@@ -368,38 +360,16 @@ class TiledDetector:
         return out[:n].clone()
 
     def detect_files(self, paths, imread=None, overlap=True):
-        """Iterate (path, Tensor[n, 7]) over image files.  overlap=True: scene i + 1 is decoded on the host and uploaded on a side stream
-        while scene i runs; the compute stream waits for its upload event (DeviceLoader's pattern)."""
-        from ..datasets.base_dataset import _default_imread
-        imread = imread or _default_imread
-        paths = list(paths)
-        main = torch.cuda.current_stream(self.device)
-        if overlap and self._side is None:
-            self._side = torch.cuda.Stream(device=self.device)
-
-        def load(path):
-            if not overlap:
-                return self._place(imread(path)), None
-            with torch.cuda.stream(self._side):
-                placed = self._place(imread(path))
-                return placed, self._side.record_event()
-
-        nxt = load(paths[0]) if paths else None
-        for i, path in enumerate(paths):
-            placed, ev = nxt
-            if ev is not None:
-                main.wait_event(ev)
-            out, num = self._enqueue(placed)
-            nxt = load(paths[i + 1]) if overlap and i + 1 < len(paths) else None
-            n = int(num.item())
-            res = out[:n].clone()
-            del placed                        # scene i is done: its side-stream memory may be reused
-            if not overlap and i + 1 < len(paths):
-                nxt = load(paths[i + 1])
-            yield path, res
+        """Iterate (path, Tensor[n, 7]) over image files: iter_async plus the count read and a copy of the rows.  overlap=True: scene
+        i + 1 is decoded on the host and uploaded on a side stream while scene i runs, since iter_async issues both before it hands
+        scene i over, and only then does the host block here on scene i's count; the compute stream waits for the upload's event
+        (DeviceLoader's pattern).  Scene i's memory follows iter_async's rule: it is released behind an event recorded after scene i's
+        launches (one record and one wait per scene), not behind this count read."""
+        for path, out, num in self.iter_async(paths, imread, overlap):
+            yield path, out[:int(num.item())].clone()
 
     def iter_async(self, paths, imread=None, overlap=True):
-        """detect_files without the count read: iterate (path, out [max_det, 7], num [1] int32), both on the device and owned by the
+        """The prefetch loop over image files: iterate (path, out [max_det, 7], num [1] int32), both on the device and owned by the
         detector as run_async returns them — valid until the consumer asks for the next scene, and whatever it launches on them must go
         to the current stream.  Nothing is read back and nothing waits for the device.  overlap=True: scene i + 1 is decoded and uploaded
         on a side stream while scene i runs; its memory is released to that stream only behind an event recorded after scene i's

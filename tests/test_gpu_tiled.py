@@ -112,11 +112,11 @@ def test_cut_bit_exact_vs_numpy_and_paste_chain():
         pool[off:off + H * W * 3] = torch.from_numpy(img.reshape(-1)).to(DEV)
         wins = [(x0, y0) for _, x0, y0 in tiled.tile_plan(H, W, S, 32)]
         wins += [(max(0, W - 100), max(0, H - 100)), (W - 3, 0), (0, H - 1)]     # windows that cross the right / bottom edges
-        table = torch.tensor([[off, H, W, x0, y0] for x0, y0 in wins], dtype=torch.int64, device=DEV)
+        table = torch.tensor([[off, H, W, x0, y0, 0] for x0, y0 in wins], dtype=torch.int64, device=DEV)      # view code 0: id
         for w0 in range(0, len(wins), B):
             n = min(B, len(wins) - w0)                                   # 12 and 4 windows: the last group is partial
             dst = torch.full((B, 3, S, S), -3.0, dtype=torch.float32, device=DEV)
-            hip.call("ryolo_tile_cut", hip.ptr(pool), hip.ptr(table), w0, n, S, hip.ptr(dst), hip.stream())
+            hip.call("ryolo_tile_cut_views", hip.ptr(pool), hip.ptr(table), w0, n, S, hip.ptr(dst), hip.stream())
             got = dst.cpu().numpy()
             for k in range(n):
                 x0, y0 = wins[w0 + k]

@@ -11,6 +11,7 @@ import torch
 
 from ryolov4_amd.synth import CFG, fill_state
 from tests import views_ref as V
+from tests.test_gpu_tiled import _np_cut
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -47,22 +48,19 @@ def test_cut_views_bit_exact(S):
         ents = [(x0, y0, v) for x0, y0 in wins for v in range(8)]               # all eight views of a window back to back: every group
         assert len(ents) % B != 0                                               # of 7 mixes views, and the last group is partial
         table = torch.tensor([[off, H, W, x0, y0, v] for x0, y0, v in ents], dtype=torch.int64, device=DEV)
-        plain = torch.tensor([[off, H, W, x0, y0] for x0, y0, _ in ents], dtype=torch.int64, device=DEV)
         exp = {}
         for e0 in range(0, len(ents), B):
             n = min(B, len(ents) - e0)
             dst = torch.full((B, 3, S, S), -3.0, dtype=torch.float32, device=DEV)
             hip.call("ryolo_tile_cut_views", hip.ptr(pool), hip.ptr(table), e0, n, S, hip.ptr(dst), hip.stream())
-            ref = torch.full((B, 3, S, S), -3.0, dtype=torch.float32, device=DEV)
-            hip.call("ryolo_tile_cut", hip.ptr(pool), hip.ptr(plain), e0, n, S, hip.ptr(ref), hip.stream())
-            got, old = dst.cpu().numpy(), ref.cpu().numpy()
+            got = dst.cpu().numpy()
             for k in range(n):
                 x0, y0, v = ents[e0 + k]
                 if (x0, y0, v) not in exp:
                     exp[(x0, y0, v)] = V.np_cut_view(img, x0, y0, S, V.NAMES[v])
                 assert np.array_equal(_bits(got[k]), _bits(exp[(x0, y0, v)])), (S, H, W, x0, y0, V.NAMES[v])
-                if v == 0:
-                    assert np.array_equal(_bits(got[k]), _bits(old[k])), "view id differs from ryolo_tile_cut"
+                if v == 0:                                                      # a restatement that shares nothing with views_ref
+                    assert np.array_equal(_bits(got[k]), _bits(_np_cut(img, x0, y0, S))), "view id differs from the plain crop"
             assert (got[n:] == -3.0).all(), "slots past the group's entries were touched"
         fill = V.np_cut_view(img, W + 5, H + 9, S, "rot90")
         assert (fill == f32(114) / f32(255)).all()
@@ -160,20 +158,28 @@ def test_collect_views_bit_exact(nc):
     mapped = np.concatenate(mapped)
     assert len(mapped) > 100 and (mapped >= -V.HALF_PI).all() and (mapped < V.HALF_PI).all()
     assert gap < 1e-2, gap
-    # view code 0 through the new entry point = ryolo_tile_collect
+    # views=("id",): the plain host shift, written out here without map_rows, on the bits; theta untouched
     ids = tiled.tile_entries(H, W, S, ov, rates, ("id",))
     pv = _plan(tiled, H, W, S, ov, B, mk, nc, rates, ("id",))
     n_id = pv.groups * B
+    assert pv.T == len(ids) and n_id > len(ids), "the last group must be partial"
+    for t in (pv.cand, pv.key, pv.fkey):
+        t.fill_(7.0)
     _feed(pv, dets[:n_id], nums[:n_id])
-    hip, _, _ = _mods()
-    geom4 = torch.cat([pv.geom, torch.zeros((len(ids), 1), device=DEV)], 1).contiguous()
-    cand2, key2, fkey2 = torch.full_like(pv.cand, 7.0), torch.full_like(pv.key, 7.0), torch.full_like(pv.fkey, 7.0)
-    for g in range(pv.groups):
-        hip.call("ryolo_tile_collect_views", hip.ptr(torch.from_numpy(np.ascontiguousarray(dets[g * B:(g + 1) * B])).to(DEV)),
-                 hip.ptr(torch.from_numpy(np.ascontiguousarray(nums[g * B:(g + 1) * B])).to(DEV)), B, mk, hip.ptr(geom4), g * B, len(ids), nc,
-                 pv.ld, S, hip.ptr(cand2), hip.ptr(key2), hip.ptr(fkey2), hip.stream())
-    assert torch.equal(cand2.view(torch.int32), pv.cand.view(torch.int32)) and torch.equal(key2.view(torch.int32), pv.key.view(torch.int32))
-    assert torch.equal(fkey2, pv.fkey)
+    cand, key, fkey = pv.cand.cpu().numpy(), pv.key.cpu().numpy(), pv.fkey.cpu().numpy()
+    ecand = np.zeros((n_id * mk, 7), dtype=f32)
+    ekey = np.full((nc, n_id * mk), -np.inf, dtype=f32)
+    for e, (ri, x0, y0, name) in enumerate(ids):
+        assert name == "id"
+        n, r = int(nums[e]), f32(rates[ri])
+        d = dets[e, :n]
+        ecand[e * mk:e * mk + n] = np.stack([(d[:, 0] + f32(x0)) / r, (d[:, 1] + f32(y0)) / r, d[:, 2] / r, d[:, 3] / r, d[:, 4], d[:, 5], d[:, 6]], 1)
+        ekey[d[:, 6].astype(np.int64), e * mk + np.arange(n)] = d[:, 5]
+        assert np.array_equal(_bits(cand[e * mk:e * mk + n, 4]), _bits(d[:, 4])), "view id changed theta's bits"
+    assert ecand.dtype == f32
+    assert np.array_equal(_bits(cand), _bits(ecand))
+    assert np.array_equal(_bits(key), _bits(ekey))
+    assert (fkey == -np.inf).all()
 
 
 # ------------------------------------------------------------------------------------------ 3. merge over views
