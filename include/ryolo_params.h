@@ -141,7 +141,8 @@ typedef struct PackEntry { const float* src; bf16_t* wf; bf16_t* wd; int Cout, C
 } PackEntry;
 
 typedef struct LossParams {
-    int mode;                 // 0 csl, 1 kfiou
+    int mode;                 // 0 csl, 1 kfiou, 2 smooth-L1-IoU, 3 KLD, 4 GWD, 5 ProbIoU (2-5: this build's extras on the kfiou head layout);
+                              // any other value: RY_ERR_ARG
     int nc, na, batch, nt, tcols;
     const float* targets;     // [nt, tcols]  (img, cls, x, y, w, h, theta[, csl x 180])
     const float* head[3];     // [B, na, gs, gs, attrs]

@@ -10,7 +10,8 @@
 //   K2a loss_match_box_kernel  one THREAD per match (r05; lane 0 of a wave per match before): differentiates the box term with
 //                            forward-mode dual numbers (CIoU with constant alpha / KFIoU closed form); the box-term gradient of the
 //                            match is parked for K2b; duplicate cells are resolved last-writer-wins via an atomicMax owner grid
-//                             and linked into a per-cell chain;
+//                             and linked into a per-cell chain (modes 3-5, the Gaussian regressions KLD / GWD / ProbIoU, run
+//                            loss_match_gauss_kernel<MODE> in its place: same bookkeeping, another regression term);
 //   K2 loss_match_kernel     one wavefront per match: the class / 180-bin CSL BCE with wave64 shuffle reductions, partial sums;
 //   K2b loss_match_grad_kernel  the owner of every matched cell sums the gradient terms of the cell's matches in ascending match
 //                            order (what autograd's index_put_(accumulate=True) does, in a FIXED order) and stores them;
@@ -435,6 +436,109 @@ __global__ __launch_bounds__(256) void loss_match_box_kernel(const LossParams p,
     f[7] = reg_b;
 }
 
+// Gaussian box regressions (EXTRA modes 3 KLD, 4 GWD, 5 ProbIoU; the reference has no code for any of them — the definitions are this
+// build's).  A box is the Gaussian N((x, y), R diag(w^2/4, h^2/4) R^T) KFLoss already uses; every quantity below is a
+// function of the two Gaussians alone, so the loss does not change under (w, h, theta) -> (h, w, theta +- pi/2) or theta -> theta +- pi.
+//   a = w^2/4, b = h^2/4, D = theta_p - theta_t, c2 = cos^2 D, s2 = sin^2 D, q = ap bp at bt
+//   T1 = (ap at + bp bt) c2 + (ap bt + bp at) s2 = tr(Sp St),   T2 = (ap bt + bp at) c2 + (ap at + bp bt) s2 = det St tr(St^-1 Sp)
+// Returns the per-match loss L in [0, 1) as a dual of (x, y, w, h, theta); the similarity 1 - L is the objectness target.
+template <int MODE>
+__device__ __forceinline__ Dual<5> gauss_dual(Dual<5> x, Dual<5> y, Dual<5> w, Dual<5> h, Dual<5> r, const float* t)
+{
+    typedef Dual<5> D;
+    const D wp = dclamp(w, 1e-4f, 1e4f), hp = dclamp(h, 1e-4f, 1e4f);
+    const float wt = fminf(fmaxf(t[2], 1e-4f), 1e4f), ht = fminf(fmaxf(t[3], 1e-4f), 1e4f), rt = t[4];
+    const D ap = wp * wp * 0.25f, bp = hp * hp * 0.25f;
+    const float at = wt * wt * 0.25f, bt = ht * ht * 0.25f;
+    const D dx = x - t[0], dy = y - t[1];
+    const D dr = r - rt;
+    const float cd = cosf(dr.v), sd = sinf(dr.v);
+    const D c2 = dscale(dr, -2.f * cd * sd, cd * cd);
+    const D s2 = dscale(dr, 2.f * sd * cd, sd * sd);
+    const D e1 = ap * at + bp * bt, e2 = ap * bt + bp * at;
+    const float ct = cosf(rt), st = sinf(rt);
+    D dist;
+    if (MODE == 3) {                                                         // D_KL(N_p || N_t)
+        const D u = dx * ct + dy * st, v = dy * ct - dx * st;                // centre offset in the target's frame
+        const D T2 = e2 * c2 + e1 * s2;
+        const D pq = ap * bp;
+        const float ab = at * bt;
+        const D lg = dscale(pq, -1.f / pq.v, logf(ab / pq.v));               // ln(at bt / (ap bp))
+        dist = (u * u * (1.f / at) + v * v * (1.f / bt) + T2 * (1.f / ab) + lg) * 0.5f - 1.f;
+        dist = dclamp(dist, 0.f, INFINITY);
+    } else if (MODE == 4) {                                                  // squared 2-Wasserstein distance
+        const D T1 = e1 * c2 + e2 * s2;
+        const D q = ap * bp * (at * bt);
+        const float rq = sqrtf(q.v);
+        const D in = T1 + dscale(q, 0.5f / rq, rq) * 2.f;                    // tr(Sp St) + 2 sqrt(det Sp det St)
+        const float ri = sqrtf(in.v);
+        dist = dx * dx + dy * dy + ap + bp + (at + bt) - dscale(in, 0.5f / ri, ri) * 2.f;
+        dist = dclamp(dist, 0.f, INFINITY);
+    } else {                                                                 // Bhattacharyya distance, S = (Sp + St) / 2
+        const float cp = cosf(r.v), sp = sinf(r.v);
+        const D cp2 = dscale(r, -2.f * cp * sp, cp * cp), sp2 = dscale(r, 2.f * sp * cp, sp * sp);
+        const D cs = dscale(r, cp * cp - sp * sp, cp * sp);
+        const D S00 = (ap * cp2 + bp * sp2 + (at * (ct * ct) + bt * (st * st))) * 0.5f;
+        const D S11 = (ap * sp2 + bp * cp2 + (at * (st * st) + bt * (ct * ct))) * 0.5f;
+        const D S01 = ((ap - bp) * cs + ((at - bt) * (ct * st))) * 0.5f;
+        const D T2 = e2 * c2 + e1 * s2;
+        const D detS = (ap * bp + (at * bt) + T2) * 0.25f;
+        const D m = dx * dx * S11 - dx * dy * S01 * 2.f + dy * dy * S00;
+        const D q = ap * bp * (at * bt);
+        const float rq = sqrtf(q.v);
+        const D ratio = detS / dscale(q, 0.5f / rq, rq);
+        dist = m / (detS * 8.f) + dscale(ratio, 1.f / ratio.v, logf(ratio.v)) * 0.5f;
+        dist = dclamp(dist, 1e-7f, 100.f);
+    }
+    if (MODE == 5) {                                                         // L = sqrt(1 - exp(-D) + eps): the Hellinger distance
+        const float l = sqrtf(-expm1f(-dist.v) + 1e-7f);
+        return dscale(dist, expf(-dist.v) / (2.f * l), l);
+    }
+    const float den = 1.f + log1pf(dist.v);                                  // L = 1 - 1 / (tau + f(D)), tau = 1, f = log1p
+    return dscale(dist, 1.f / (den * den * (1.f + dist.v)), 1.f - 1.f / den);
+}
+
+// K2a of the Gaussian modes: a kernel of its own, one instantiation per mode, so that loss_match_box_kernel (modes 0-2) compiles to what it
+// compiled to before these modes existed (registers, scratch).  Same thread -> match mapping, decode, owner / chain bookkeeping and record
+// slots as the kfiou branch above; only the regression term and the score differ.
+template <int MODE>
+__global__ __launch_bounds__(256) void loss_match_gauss_kernel(const LossParams p, ScaleWs s0, ScaleWs s1, ScaleWs s2)
+{
+    const int scale = blockIdx.y;
+    const ScaleWs s = scale == 0 ? s0 : (scale == 1 ? s1 : s2);
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    const int n = *s.count;
+    if (e >= n) return;
+    const int attrs = p.nc + 6;
+    const int* r = s.rec + (int64_t)e * 8;
+    float* f = s.frec + (int64_t)e * 8;
+    const int a = r[1], cell = r[6];
+    const float* ps = p.head[scale] + (int64_t)cell * attrs;
+    const float inv_n = 1.0f / (float)n;
+    const float aw = p.anchors[scale][a][0], ah = p.anchors[scale][a][1];
+    const float sx = sigm(ps[0]), sy = sigm(ps[1]), sw = sigm(ps[2]), sh = sigm(ps[3]), sa = sigm(ps[4]);
+    float pa = (sa - 0.5f) * 1.1f + p.anchors[scale][a][2];
+    const float hp = (float)(3.14159265358979323846 / 2);
+    if (pa >= hp) pa = pa - PI_F;
+    if (pa < -hp) pa = pa + PI_F;
+    const Dual<5> L = gauss_dual<MODE>(dvar<5>(sx * 2.f - 0.5f, 0), dvar<5>(sy * 2.f - 0.5f, 1), dvar<5>((sw * 2.f) * (sw * 2.f) * aw, 2),
+                                       dvar<5>((sh * 2.f) * (sh * 2.f) * ah, 3), dvar<5>(pa, 4), f);
+    f[5] = fmaxf(1.f - L.v, 0.f);
+    atomicMax(&s.owner[cell], e);                                            // last writer (largest e) wins
+    if (p.compute_grad) {
+        const float k = p.box * inv_n;
+        float* gb = s.gbox + (int64_t)e * 8;
+        gb[0] = k * L.d[0] * 2.f * sx * (1.f - sx);
+        gb[1] = k * L.d[1] * 2.f * sy * (1.f - sy);
+        gb[2] = k * L.d[2] * 8.f * sw * sw * (1.f - sw) * aw;
+        gb[3] = k * L.d[3] * 8.f * sh * sh * (1.f - sh) * ah;
+        gb[4] = k * L.d[4] * 1.1f * sa * (1.f - sa);
+        s.next[e] = atomicExch(&s.head[cell], e);
+    }
+    f[6] = L.v;
+    f[7] = 0.f;
+}
+
 // K2b, class / angle-bin BCE terms: G lanes per match — 64 (a wave per match), or 16 when the classes fit (nc <= 16, no angle bins: four matches
 // per wave; the xor butterfly over 16 lanes adds the same values in the same order as the 64-lane one did, whose upper lanes held zeros) — and
 // folds the match's box terms into the partial sums: one row of part_match per FOUR consecutive matches, as before.
@@ -694,9 +798,12 @@ __global__ __launch_bounds__(1024) void loss_finalize_kernel(const LossParams p,
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI
+// LossParams.mode: 0 csl, 1 kfiou, 2 smooth-L1-IoU, 3 KLD, 4 GWD, 5 ProbIoU; anything else is refused (it used to run as kfiou)
+static inline bool loss_mode_ok(int mode) { return mode >= 0 && mode <= 5; }
+
 extern "C" int ryolo_loss_workspace_bytes(const LossParams* pp, size_t* bytes)
 {
-    if (!pp || !bytes) return RY_ERR_ARG;
+    if (!pp || !bytes || !loss_mode_ok(pp->mode)) return RY_ERR_ARG;
     LossParams p = *pp;
     p.ws = nullptr;
     ScaleWs s[3];
@@ -706,7 +813,7 @@ extern "C" int ryolo_loss_workspace_bytes(const LossParams* pp, size_t* bytes)
 
 extern "C" int ryolo_loss(const LossParams* pp, hipStream_t stream)
 {
-    if (!pp) return RY_ERR_ARG;
+    if (!pp || !loss_mode_ok(pp->mode)) return RY_ERR_ARG;
     const LossParams& p = *pp;
     if (p.na < 1 || p.na > LOSS_MAX_NA || p.nt < 0 || p.batch < 1 || p.nc < 0 || !p.items || !p.ws) return RY_ERR_ARG;
     if (p.nt > 0 && !p.targets) return RY_ERR_ARG;
@@ -726,7 +833,11 @@ extern "C" int ryolo_loss(const LossParams* pp, hipStream_t stream)
     if (p.nt > 0) {                                           // (one launch per pass for the three scales: blockIdx.y; cap is the same for all)
         hipLaunchKernelGGL(loss_targets_count_kernel, dim3(3, LT_BLOCKS), dim3(1024), 0, stream, p, s[0], s[1], s[2]);
         hipLaunchKernelGGL(loss_targets_kernel, dim3(3, LT_BLOCKS), dim3(1024), 0, stream, p, s[0], s[1], s[2]);
-        hipLaunchKernelGGL(loss_match_box_kernel, dim3((unsigned)ry_cdiv(s[0].cap, 256), 3), dim3(256), 0, stream, p, s[0], s[1], s[2]);
+        const dim3 gbox((unsigned)ry_cdiv(s[0].cap, 256), 3);
+        if (p.mode == 3) hipLaunchKernelGGL(loss_match_gauss_kernel<3>, gbox, dim3(256), 0, stream, p, s[0], s[1], s[2]);
+        else if (p.mode == 4) hipLaunchKernelGGL(loss_match_gauss_kernel<4>, gbox, dim3(256), 0, stream, p, s[0], s[1], s[2]);
+        else if (p.mode == 5) hipLaunchKernelGGL(loss_match_gauss_kernel<5>, gbox, dim3(256), 0, stream, p, s[0], s[1], s[2]);
+        else hipLaunchKernelGGL(loss_match_box_kernel, gbox, dim3(256), 0, stream, p, s[0], s[1], s[2]);
         const int G = (p.mode != 0 && p.nc <= 16) ? 16 : 64;
         hipLaunchKernelGGL(loss_match_kernel, dim3((unsigned)ry_cdiv(s[0].cap, 256 / G), 3), dim3(256), 0, stream, p, s[0], s[1], s[2], G);
         if (p.compute_grad) hipLaunchKernelGGL(loss_match_grad_kernel, dim3(s[0].nblk_match, 3), dim3(256), 0, stream, p, s[0], s[1], s[2]);
@@ -741,7 +852,7 @@ extern "C" int ryolo_loss(const LossParams* pp, hipStream_t stream)
 // valid until the next ryolo_loss on the same workspace
 extern "C" int ryolo_loss_owner_grids(const LossParams* pp, const int** owner)
 {
-    if (!pp || !owner || !pp->ws) return RY_ERR_ARG;
+    if (!pp || !owner || !pp->ws || !loss_mode_ok(pp->mode)) return RY_ERR_ARG;
     LossParams p = *pp;
     ScaleWs s[3];
     size_t need;
@@ -755,7 +866,7 @@ extern "C" int ryolo_loss_owner_grids(const LossParams* pp, const int** owner)
 // (b, a, gj, gi, cls, target row, cell, pad) in the reference's enumeration order (tests: target-assignment parity)
 extern "C" int ryolo_loss_match_records(const LossParams* pp, const int** count, const int** rec)
 {
-    if (!pp || !count || !rec || !pp->ws) return RY_ERR_ARG;
+    if (!pp || !count || !rec || !pp->ws || !loss_mode_ok(pp->mode)) return RY_ERR_ARG;
     LossParams p = *pp;
     ScaleWs s[3];
     size_t need;

@@ -141,7 +141,7 @@ class _ComputeLossBase:
     def _run(self, outputs, targets, compute_grad):
         S.check_layouts()
         dev = outputs[0].device
-        attrs = self.nc + (185 if self.MODE == 0 else 6)              # (MODE 2 shares the kfiou head layout)
+        attrs = self.nc + (185 if self.MODE == 0 else 6)              # (MODEs 2-5 share the kfiou head layout)
         outs = []
         for o in outputs:
             hip.require_device(o, "loss")
@@ -258,3 +258,44 @@ class ComputeSL1IoULoss(_ComputeLossBase):
     DESIGN.md §4.3; oracle: oracle/ref_ops.sl1iou_loss, fp64, written for this build — no reference oracle exists)."""
     MODE = 2
     KEYS = ("reg_loss", "conf_loss", "cls_loss", "total_loss")
+
+
+# EXTRA modes 3-5, not in the reference's code: box regressions on the Gaussian N((x, y), R diag(w^2/4, h^2/4) R^T) that KFLoss already models a
+# box as (xywhr2xywhrsigma).  Same constructor / call / loss_items contract as ComputeKFIoULoss and the SAME network (Yolo(mode='kfiou'): 18
+# rotated anchors, attrs = nc + 6), same target assignment, class and objectness terms; only the regression term differs, and there is no
+# separately weighted centre term (the centre offset sits inside the distance).  The objectness target of a match is the similarity 1 - L the
+# loss defines.  Definitions: DESIGN.md §4.3; fp64 restatement: tests/gauss_loss_ref.py, written for this build — no reference oracle exists.
+# Which of them gives the better mAP on DOTA has not been measured.
+class ComputeKLDLoss(_ComputeLossBase):
+    """Kullback-Leibler divergence D_KL(N_pred || N_target) (Yang et al., NeurIPS 2021, arXiv 2106.01883), L = 1 - 1 / (1 + log1p(D))."""
+    MODE = 3
+    KEYS = ComputeKFIoULoss.KEYS
+
+
+class ComputeGWDLoss(_ComputeLossBase):
+    """Squared Gaussian Wasserstein distance (Yang et al., ICML 2021, arXiv 2101.11952), L = 1 - 1 / (1 + log1p(D))."""
+    MODE = 4
+    KEYS = ComputeKFIoULoss.KEYS
+
+
+class ComputeProbIoULoss(_ComputeLossBase):
+    """Bhattacharyya distance B in its Hellinger form L = sqrt(1 - exp(-B)); 1 - L is ProbIoU (Llerena et al., arXiv 2106.06072)."""
+    MODE = 5
+    KEYS = ComputeKFIoULoss.KEYS
+
+
+LOSSES = {
+    "csl": ComputeCSLLoss,            # Yolo(mode="csl")
+    "kfiou": ComputeKFIoULoss,        # every other name: Yolo(mode="kfiou")
+    "sl1iou": ComputeSL1IoULoss,
+    "kld": ComputeKLDLoss,
+    "gwd": ComputeGWDLoss,
+    "probiou": ComputeProbIoULoss,
+}
+
+
+def make_loss(name, model, hyp):
+    """The criterion called `name` (a key of LOSSES) for `model`."""
+    if name not in LOSSES:
+        raise ValueError("unknown loss {!r}: choose one of {}".format(name, ", ".join(sorted(LOSSES))))
+    return LOSSES[name](model, hyp)

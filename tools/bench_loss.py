@@ -1,0 +1,73 @@
+"""Time of the fused loss alone — one `criterion(outs, targets, sync_items=False)` + `backward()` — at the benchmark shape (batch 64,
+800x800, nc 16, synth_batch targets, random head maps) for the losses that share the kfiou head layout.  Device events around `--iters`
+calls after `--warmup`, the whole round repeated `--runs` times with the losses alternating, so that the spread of one loss across the
+runs can be read next to the differences between losses.  Prints one JSON line.
+
+    python tools/bench_loss.py [--losses kfiou,kld,gwd,probiou] [--batch 64] [--size 800] [--iters 50] [--warmup 10] [--runs 2]
+
+RYOLO_LIB=<another build of libryolo_hip.so> times that build instead (A/B against another commit)."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+from ryolov4_amd import hip
+from ryolov4_amd.lib.loss import make_loss
+from ryolov4_amd.synth import CFG, HYP, synth_batch
+
+
+class _Model:
+    pass
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--losses", default="kfiou,kld,gwd,probiou")
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--size", type=int, default=800)
+    ap.add_argument("--nc", type=int, default=16)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--runs", type=int, default=2)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_loss: needs the GPU (there is no CPU path to time)")
+    dev = torch.device("cuda:0")
+    from oracle import ref_ops
+    m = _Model()
+    m.anchors, m.nc = ref_ops.make_anchors(CFG, "kfiou"), args.nc
+    _, tg = synth_batch(args.batch, args.size, args.nc, False, seed=42)
+    tg = tg.to(dev)
+    g = torch.Generator(device=dev).manual_seed(9)
+    outs = [torch.randn(args.batch, 18, args.size // s, args.size // s, args.nc + 6, generator=g, device=dev).requires_grad_() for s in (8, 16, 32)]
+    names = args.losses.split(",")
+    crits = {n: make_loss(n, m, HYP) for n in names}
+
+    def call(crit):
+        loss, _ = crit(outs, tg, sync_items=False)
+        loss.backward()
+        for o in outs:
+            o.grad = None
+
+    ms = {n: [] for n in names}
+    for _ in range(args.runs):
+        for n in names:
+            for _ in range(args.warmup):
+                call(crits[n])
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(args.iters):
+                call(crits[n])
+            t1.record()
+            torch.cuda.synchronize()
+            ms[n].append(round(t0.elapsed_time(t1) / args.iters, 4))
+            crits[n].flush()
+    print(json.dumps({"what": "fused loss forward + backward, ms per call (device events)", "lib": os.path.basename(os.path.dirname(hip.LIB_PATH)) + "/" + os.path.basename(hip.LIB_PATH),
+                      "batch": args.batch, "size": args.size, "nc": args.nc, "targets": int(tg.shape[0]), "iters": args.iters, "warmup": args.warmup,
+                      "ms_per_call": ms}))
+
+
+if __name__ == "__main__":
+    main()
