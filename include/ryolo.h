@@ -482,6 +482,38 @@ int ryolo_resize_hsv_windows(const uint8_t* pool, const void* items_dev, int nit
 int ryolo_scene_label_rows(void* rows_dev, int64_t nrows, const int32_t* win_of_row, const int32_t* wins, int nwin, double iof_thr,
                            double* iof_out, ryolo_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Anchors fitted to a dataset, and the labels no anchor reaches (csrc/anchors.hip; lib/anchors.py).  The reference has no
+ * such stage (its anchors are constants); tests/anchor_ref.py restates these semantics in numpy.  No allocation, no synchronisation,
+ * capturable; no float atomics: every sum runs in a fixed order that depends on n alone, in double; counts are integers.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* Which target rows the loss can assign.  Reads of `p` only: targets [nt][tcols] (normalised, the loss's layout), nt, tcols, na, anchors, gs,
+ * mode.  counts int32 [nt][3]: per row and scale the number of anchors that pass the loss's rule — both side ratios max(r, 1 / r) < 4 with
+ * r = fl32(t * gs) / anchor, modes != 0 also |cos(theta - anchor angle)| > 0.866, the float operations of the loss's target assignment.  The
+ * image index (column 0) is NOT looked at.  summary int64 [5]: rows reached on scale 0, 1, 2; rows reached on no scale (lost); anchor
+ * passes over all rows and scales.  nt == 0: summary is zeroed, counts untouched. */
+int ryolo_anchor_reach(const LossParams* p, int32_t* counts, int64_t* summary, ryolo_stream_t stream);
+/* Sizes wh float32 [n][2] in pixels of the network input (finite, > 0), anchor set k float32 [K][2], 1 <= K <= 32, 1 <= n < 2^31.  Per label
+ * x = max over anchors of min(min(rw, 1 / rw), min(rh, 1 / rh)), r = wh / k in float32; the label is reached iff x > (float)(1 / thr).
+ * stats (device, 4 x 8 bytes): [0] fitness = (1 / n) * sum of x over the reached labels, a DOUBLE; [1] reached labels, [2] (label, anchor)
+ * pairs whose own minimum passes, [3] accepted generations, int64.  Workspace: ryolo_anchor_workspace_bytes. */
+int ryolo_anchor_workspace_bytes(int64_t n, size_t* bytes);
+int ryolo_anchor_fitness(const float* wh, int64_t n, const float* k, int K, double thr, void* workspace, size_t workspace_bytes, int64_t* stats,
+                         ryolo_stream_t stream);
+/* (1 + C) evolution strategy, 1 <= C <= 16, G >= 0 generations, mutation table v float32 [G][C][K][2] on the device: the children of
+ * generation g are max(k * v[g][c], 2.0f); the child of greatest fitness (lowest c among equals) replaces k iff its fitness is strictly
+ * greater than k's.  One pass over the labels and one single-workgroup launch per generation; the decision is made on the device.  k is
+ * read and overwritten; stats as above, for the final k. */
+int ryolo_anchor_evolve(const float* wh, int64_t n, float* k, int K, const float* v, int G, int C, double thr, void* workspace,
+                        size_t workspace_bytes, int64_t* stats, ryolo_stream_t stream);
+/* Lloyd's k-means on (w, h), n <= 2^24.  init != 0: k = the labels at ranks floor((j + 0.5) / K * n) of the labels in ascending order of
+ * fl32(w * h) (ryolo_argsort_desc read backwards: among equal areas the HIGHER index comes first); else k holds the start.  Per iteration:
+ * nearest centroid by fl32(dw * dw + dh * dh), unfused, lowest centroid among equals; new centroid = (float)(double sum / count); an empty
+ * cluster keeps its centroid.  assign (optional, int32 [n]): the assignment the LAST iteration made. */
+int ryolo_anchor_kmeans_workspace_bytes(int64_t n, size_t* bytes);
+int ryolo_anchor_kmeans(const float* wh, int64_t n, float* k, int K, int iters, int init, int32_t* assign, void* workspace,
+                        size_t workspace_bytes, ryolo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

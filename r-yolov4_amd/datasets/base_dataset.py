@@ -236,11 +236,10 @@ class BaseDataset:
         """load_image (base_dataset.py:170-186) as a table row: resized size, interpolation, the hsv tables of this use.
         Returns (row index into `items`, (h0, w0), (h, w))."""
         h0, w0 = self._use_shape(index, len(items))
-        r = self.img_size / max(h0, w0)
-        h, w, interp = h0, w0, A.INTERP_COPY
+        r, (h, w) = self._resized(h0, w0)
+        interp = A.INTERP_COPY
         if r != 1:
             interp = A.INTERP_AREA if (r < 1 and not self.augment) else A.INTERP_LINEAR
-            w, h = int(w0 * r), int(h0 * r)
         lut = -1
         hy = self.hyp
         if self.augment and (hy["hsv_h"] or hy["hsv_s"] or hy["hsv_v"]):
@@ -249,6 +248,16 @@ class BaseDataset:
             luts.append(A.hsv_luts(gains))
         items.append((index, (h, w), interp, lut))
         return len(items) - 1, (h0, w0), (h, w)
+
+    def _resized(self, h0, w0):
+        """load_image's size rule (base_dataset.py:174-180): (ratio r, (h, w) after the resize to img_size on the longer side)."""
+        r = self.img_size / max(h0, w0)
+        return r, ((h0, w0) if r == 1 else (int(h0 * r), int(w0 * r)))
+
+    def _letterbox_plan(self, hw):
+        """The letterbox of a resized (h, w) onto the img_size square: ((nh, nw), (top, bottom, left, right), pad)."""
+        (nw, nh), edges, pad = A.pad_to_square_plan(hw, (self.img_size, self.img_size))
+        return (nh, nw), edges, pad
 
     def _mosaic_plan(self, index, nine, items, luts):
         rnd, s, n = self.rng[0], self.img_size, len(self.img_files)
@@ -297,7 +306,7 @@ class BaseDataset:
                     mixes.append((out_of[-1], len(canvases) - 1, nrd.beta(8.0, 8.0)))
             else:
                 k, hw0, hw = self._load_image_plan(index, items, luts)
-                (nw, nh), (top, bottom, left, right), pad = A.pad_to_square_plan(hw, (s, s))
+                (nh, nw), (top, bottom, left, right), pad = self._letterbox_plan(hw)
                 cv = dict(kind="letterbox", item=k, hw0=hw0, hw=hw, new=(nh, nw), edges=(top, bottom, left, right), pad=pad, index=index, slot=slot,
                           M=None)
                 if self.augment:
@@ -358,6 +367,42 @@ class BaseDataset:
         targets10 = A.label_stage_table(self._label_table(rows) if len(rows) else None, len(rows), np.stack(mats) if mats else None, dev)
         imgs, targets = finalize_batch(final, targets10, A._to_device(flags, dev), self.csl)
         return [self.img_files[i] for i in indices], imgs, targets
+
+    # ------------------------------------------------------------------ labels alone
+    def label_table(self, indices=None, chunk=4096):
+        """Labels as the network sees them, without pixels: float32 [n, 7] = (item, cls, x, y, w, h, theta) on the device, bit-equal to the
+        first seven columns of what assemble_batch returns for an augment=False twin of this dataset (plain letterbox path; for scenes the
+        planned windows, jitter off), with the dataset index of the item in column 0 instead of the batch slot.  Only the label half of a
+        batch runs (_use_shape, _use_labels, _label_table, ryolo_label_stage, ryolo_encode_labels), `chunk` items at a time; no random
+        number is drawn, and no pixel is touched when the image shapes are known (file headers, set_arrays).  lib/anchors.py reads the
+        label sizes of a whole split from this."""
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f"label_table: chunk must be >= 1, got {chunk}")
+        self.cache()
+        indices = list(range(len(self))) if indices is None else [int(i) for i in indices]
+        out = [self._label_chunk(indices[a:a + chunk]) for a in range(0, len(indices), chunk)]
+        return torch.cat(out) if out else torch.empty((0, 7), dtype=torch.float32, device=self.device)
+
+    def _label_chunk(self, indices):
+        s, dev = self.img_size, self.device
+        rows = []
+        for row, index in enumerate(indices):
+            h0, w0 = self._use_shape(index, row)
+            _, hw = self._resized(h0, w0)                              # the two rules assemble_batch's letterbox branch uses
+            _, _, pad = self._letterbox_plan(hw)
+            polys, cls = self._use_labels(index, row)
+            rows.append(A.label_rows(polys, cls, row, (h0, w0), hw, A.Use(row, None, pad, None, None), -1, self.normalized_labels))
+        rows = np.concatenate(rows) if rows else np.zeros(0, dtype=A.LABEL_ROW_DTYPE)
+        nt = len(rows)
+        out = torch.empty((nt, 7), dtype=torch.float32, device=dev)
+        if not nt:
+            return out
+        targets10 = A.label_stage_table(self._label_table(rows), nt, None, dev)
+        item_of_slot = A._to_device(np.asarray(indices, dtype=np.int32), dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        hip.call("ryolo_encode_labels", hip.ptr(targets10), nt, s, s, None, hip.ptr(item_of_slot), 0, hip.ptr(out), count.data_ptr(), None, hip.stream())
+        return out[:int(count.item())]                                 # (the row count: one host read per chunk, as finalize_batch)
 
     # ------------------------------------------------------------------ API parity with torch.utils.data.Dataset users
     def __getitem__(self, index):

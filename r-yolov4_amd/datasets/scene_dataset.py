@@ -216,6 +216,16 @@ class SceneDataset(BaseDataset):
         self.last_windows, self._row_wins = [], []
         return super().assemble_batch(indices)
 
+    def _label_chunk(self, indices):
+        """BaseDataset._label_chunk over the PLANNED windows: jitter is off for its duration (the window generator is not touched) and the
+        window tables of the last batch are put back afterwards."""
+        saved = self.jitter, self.last_windows, self._row_wins
+        self.jitter, self.last_windows, self._row_wins = False, [], []
+        try:
+            return super()._label_chunk(indices)
+        finally:
+            self.jitter, self.last_windows, self._row_wins = saved
+
 
 class DOTASceneDataset(SceneDataset):
     """Full-size DOTA scenes in DOTADataset's layout: `images/*.png` with `annfiles/*.txt` (datasets/DOTA_dataset.py)."""

@@ -122,6 +122,7 @@ for _name, _sig in {
     "ryolo_loss_grad_scale": [P, L, P, P],
     "ryolo_loss_grad_scale_multi": [_PTR(P * 8), _PTR(L * 8), I, P, P],
     "ryolo_loss_match_records": [_PTR(LossParams), _PTR(P * 3), _PTR(P * 3)],
+    "ryolo_anchor_reach": [_PTR(LossParams), P, P, P],
 }.items():
     hip.register(_name, _sig)
 
