@@ -114,6 +114,51 @@ int ryolo_scene_match(const float* dets, const int32_t* num, int64_t max_det, co
                       const float* iouv, int niou, unsigned char* tp, float* conf, float* pcls, int64_t cap, int64_t* cursor, int32_t* overflow,
                       void* workspace, size_t workspace_bytes, ryolo_stream_t stream);
 
+/* The matching of the DOTA / VOC protocol for ONE full scene, in ryolo_scene_match's launch shape and with its accumulators
+ * (lib/dota_eval.py; tests/dota_eval_ref.py restates it in numpy).  dets / num / max_det / cls_off / nc / niou / iouv / cap / cursor /
+ * overflow: as for ryolo_scene_match; dets is only read.
+ * labels [nl,15] = (cls, difficult, quad x1 y1 .. x4 y4, rect x y w h theta_rad) GROUPED BY CLASS ascending, the caller's order kept
+ * inside a class.  The quad is used as annotated when its eight coordinates are finite and it is strictly convex (the four edge cross
+ * products all of one non-zero sign); otherwise the four corners of `rect` (its xyxyxyxy2xywha rectangle, or the caller's box when the
+ * labels were boxes: quad = NaN) take its place.  Either orientation is accepted (normalised by the sign of the shoelace area).
+ * Rule, per threshold k.  IoU(i, t) in float64: the corners of detection i's rectangle, x + (dx cos + dy sin), y + (dy cos - dx sin) with
+ * (dx, dy) = (-+h/2, -+w/2), are clipped against label t's quad by four Sutherland-Hodgman half-plane steps (a vertex on an edge is
+ * inside; at most 8 vertices); IoU = inter / (area_det + area_label - inter), 0 when that denominator is <= 0.  Pairs with disjoint
+ * axis-aligned bounds have IoU 0 without the clip, and so has every pair with a non-finite detection rectangle or label.
+ *   best(i)     = the label of detection i's class with the largest IoU, difficult labels included; none for a class that is not an
+ *                 integer in [0, nc) (NaN included) or has no label
+ *   owner_k(t)  = the SMALLEST i with best(i) == t and IoU(i, t) > iouv[k]
+ *   status[i][k] = 2 (ignored)  if IoU(i, best) > iouv[k] and best is difficult
+ *                  1 (TP)       if IoU(i, best) > iouv[k], best is not difficult and owner_k(best) == i
+ *                  0 (FP)       otherwise: a duplicate, an IoU at or below the threshold, no best label, a bad class
+ *   npos[c]    += the labels of class c that are not difficult (int64 [nc] on the device, zeroed by the caller before the first scene)
+ * Ties.  Equal IoU: the first label in the caller's order inside the class.  Equal score: the smaller row claims first.  IoU exactly
+ * equal to a threshold is not above it; thresholds are float32 values compared in float64.
+ * Accumulators: status [cap][niou] bytes, conf [cap], pcls [cap]; rows cur .. cur + n - 1 are written and the cursor advances by n; if
+ * cur + n > cap nothing is written, the cursor and npos stay and *overflow = 1.  max_det == 0 is legal: only npos moves.
+ * Launches: label prologue (quad or rectangle, orientation, vertices / area / bounds in float64, owner[nl][niou] reset), one wave per
+ * detection (clip, first maximum, one atomicMin per threshold exceeded), a thread per detection (rows), the cursor and npos.
+ * Deterministic, no float atomics, no host read, capturable.  Every index that comes from data is clamped or checked as in
+ * ryolo_scene_match.  After the call the first max_det doubles of the workspace hold IoU(i, best(i)) per detection row (-1: no label
+ * of its class; rows >= *num are not written) — read by the tests. */
+int ryolo_dota_match_workspace_bytes(int64_t max_det, int64_t nl, int niou, size_t* bytes);
+int ryolo_dota_match(const float* dets, const int32_t* num, int64_t max_det, const float* labels, const int32_t* cls_off, int64_t nl, int nc,
+                     const float* iouv, int niou, unsigned char* status, float* conf, float* pcls, int64_t cap, int64_t* cursor,
+                     int32_t* overflow, int64_t* npos, void* workspace, size_t workspace_bytes, ryolo_stream_t stream);
+
+/* VOC AP from the accumulated rows of ryolo_dota_match, on the device.  status [n][niou] bytes (1 TP, 2 ignored, anything else FP),
+ * conf / pred_cls [n] fp32, npos [nc] int64 (device), grid11 [11] float64 on the device (np.arange(0., 1.1, 0.1) from the host).
+ * Per class c and threshold k: the rows of class c by confidence descending (equal confidence: the earlier row first), rows with
+ * status 2 skipped; running counts tpc / fpc; rec = tpc / npos[c]; prec = tpc / max(tpc + fpc, 2.220446049250313e-16).
+ *   metric 0 (voc07): ap = 0; for t in grid11: ap = ap + max(prec[rec >= t], 0 when there is none) / 11.0
+ *   metric 1 (voc12): mrec = [0, rec.., 1], mpre = [0, prec.., 0] made non-increasing from the right; the sum of
+ *                     (mrec[j+1] - mrec[j]) * mpre[j+1] over the j where mrec changes, added in ascending order one after the other
+ * Out: ap [nc][niou] float64 (NaN for a class with npos <= 0, 0 for one with positives and no counted row), n_pred [nc] int64 = rows of
+ * each class, ignored ones included.  n < 2^31 - 1, nc <= 256, niou <= 16.  No host synchronisation. */
+int ryolo_ap_voc_workspace_bytes(int64_t n, int niou, int nc, size_t* bytes);
+int ryolo_ap_voc(const unsigned char* status, const float* conf, const float* pred_cls, int64_t n, const int64_t* npos, int nc, int niou,
+                 int metric, const double* grid11, void* workspace, size_t workspace_bytes, double* ap, int64_t* n_pred, ryolo_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * YoloLayer — replaces model/yololayer.py:15-56 (YoloCSLLayer.forward) and :66-105 (YoloKFIoULayer.forward).
  * ------------------------------------------------------------------------------------------------------------ */

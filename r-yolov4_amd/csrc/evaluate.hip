@@ -479,3 +479,480 @@ extern "C" int ryolo_scene_match(const float* dets, const int32_t* num, int64_t 
     RY_CHECK_LAUNCH();
     return RY_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ DOTA-protocol matching
+// The dataset's own rule (include/ryolo.h: ryolo_dota_match) in ryolo_scene_match's launch shape.  What differs: the labels are the
+// annotated quadrilaterals, the IoU is a float64 Sutherland-Hodgman clip of the detection's rectangle against the label's quad, every
+// threshold has its own owner table, and a detection whose best label is "difficult" is ignored (status 2) instead of counted.
+// The clip never holds more than 8 vertices (a convex quad cut by four half-planes); it lives in fixed-size arrays, every loop is
+// unrolled and an append is a chain of selects, so nothing is indexed by a run-time value.
+#define DM_WAVES 4
+#define DM_PREP 14      // doubles per prepared label: 4 vertices (x, y) counter-clockwise, area, min x, max x, min y, max y, difficult
+#define DM_LABEL 15     // floats per label row: cls, difficult, quad[8], rect[5]
+
+static inline size_t dm_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// corners of (x, y, w, h, theta_rad) in float64: h runs along x before the rotation (lib/general.py: xywha2xyxyxyxy)
+__device__ __forceinline__ void dm_rect_corners(const float* __restrict__ b, double (&vx)[4], double (&vy)[4])
+{
+    const double x = (double)b[0], y = (double)b[1], hy = (double)b[2] / 2.0, hx = (double)b[3] / 2.0, th = (double)b[4];
+    const double c = cos(th), s = sin(th);
+    const double dx[4] = {-hx, hx, hx, -hx}, dy[4] = {-hy, -hy, hy, hy};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        vx[k] = x + (dx[k] * c + dy[k] * s);
+        vy[k] = y + (dy[k] * c - dx[k] * s);
+    }
+}
+
+// twice the signed area of the first n vertices as a fan around vertex 0, terms added in ascending order
+template <int N>
+__device__ __forceinline__ double dm_fan(const double (&px)[N], const double (&py)[N], int n)
+{
+    double s = 0.0;
+#pragma unroll
+    for (int j = 1; j + 1 < N; j++)
+        if (j + 1 < n) s += (px[j] - px[0]) * (py[j + 1] - py[0]) - (px[j + 1] - px[0]) * (py[j] - py[0]);
+    return s;
+}
+
+__device__ __forceinline__ bool dm_finite4(const double (&vx)[4], const double (&vy)[4])
+{
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 4; k++) ok = ok && isfinite(vx[k]) && isfinite(vy[k]);
+    return ok;
+}
+
+__global__ __launch_bounds__(256) void dota_prep_kernel(const float* __restrict__ labels, int64_t nl, int niou, double* __restrict__ prep,
+                                                        int32_t* __restrict__ owner)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nl) return;
+    const float* r = labels + t * DM_LABEL;
+    double vx[4], vy[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) { vx[k] = (double)r[2 + 2 * k]; vy[k] = (double)r[3 + 2 * k]; }
+    bool quad = dm_finite4(vx, vy);
+    if (quad) {                                                       // strictly convex: the four turns all of one non-zero sign
+        bool pos = true, neg = true;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const int f = (e + 1) & 3, g = (e + 2) & 3;
+            const double cr = (vx[f] - vx[e]) * (vy[g] - vy[f]) - (vy[f] - vy[e]) * (vx[g] - vx[f]);
+            pos = pos && cr > 0.0;
+            neg = neg && cr < 0.0;
+        }
+        quad = pos || neg;
+    }
+    if (!quad) dm_rect_corners(r + 10, vx, vy);
+    const bool live = dm_finite4(vx, vy);
+    const double s = dm_fan<4>(vx, vy, 4);
+    if (s < 0.0) {                                                    // clockwise in these axes: walk it the other way round
+        double u = vx[1]; vx[1] = vx[3]; vx[3] = u;
+        u = vy[1]; vy[1] = vy[3]; vy[3] = u;
+    }
+    double* p = prep + t * DM_PREP;
+    double x0 = vx[0], x1 = vx[0], y0 = vy[0], y1 = vy[0];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        p[2 * k] = vx[k];
+        p[2 * k + 1] = vy[k];
+        x0 = vx[k] < x0 ? vx[k] : x0; x1 = vx[k] > x1 ? vx[k] : x1;
+        y0 = vy[k] < y0 ? vy[k] : y0; y1 = vy[k] > y1 ? vy[k] : y1;
+    }
+    const double inf = __builtin_huge_val();
+    p[8] = 0.5 * fabs(s);
+    p[9] = live ? x0 : inf;                                           // a label without finite vertices has empty bounds: IoU 0 with everything
+    p[10] = live ? x1 : -inf;
+    p[11] = live ? y0 : inf;
+    p[12] = live ? y1 : -inf;
+    p[13] = r[1] != 0.f ? 1.0 : 0.0;                                  // NaN counts as difficult
+    for (int k = 0; k < niou; k++) owner[t * niou + k] = INT_MAX;
+}
+
+#define DM_APPEND(X, Y)                                           \
+    {                                                             \
+        _Pragma("unroll") for (int q_ = 0; q_ < 8; q_++)          \
+            if (m == q_) { qx[q_] = (X); qy[q_] = (Y); }          \
+        m += m < 8 ? 1 : 0;                                       \
+    }
+
+// area of (detection rectangle) ∩ (label quad L, counter-clockwise): four half-plane steps, a vertex on an edge is inside
+__device__ __forceinline__ double dm_clip_area(const double (&dx)[4], const double (&dy)[4], const double* __restrict__ L)
+{
+    double px[8], py[8];
+    int n = 4;
+#pragma unroll
+    for (int k = 0; k < 8; k++) { px[k] = k < 4 ? dx[k] : 0.0; py[k] = k < 4 ? dy[k] : 0.0; }
+    double lx[4], ly[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) { lx[k] = L[2 * k]; ly[k] = L[2 * k + 1]; }
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        const double ax = lx[e], ay = ly[e], ex = lx[(e + 1) & 3] - ax, ey = ly[(e + 1) & 3] - ay;
+        double d[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) d[j] = ex * (py[j] - ay) - ey * (px[j] - ax);
+        double prx = px[0], pry = py[0], prd = d[0];                  // the vertex before vertex 0: vertex n - 1
+#pragma unroll
+        for (int j = 1; j < 8; j++)
+            if (j == n - 1) { prx = px[j]; pry = py[j]; prd = d[j]; }
+        double qx[8], qy[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) { qx[k] = 0.0; qy[k] = 0.0; }
+        int m = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            if (j < n) {
+                const bool ic = d[j] >= 0.0, ip = prd >= 0.0;
+                if (ic != ip) {
+                    const double u = prd / (prd - d[j]);
+                    const double ix = prx + (px[j] - prx) * u, iy = pry + (py[j] - pry) * u;
+                    DM_APPEND(ix, iy)
+                }
+                if (ic) DM_APPEND(px[j], py[j])
+            }
+            prx = px[j]; pry = py[j]; prd = d[j];
+        }
+#pragma unroll
+        for (int k = 0; k < 8; k++) { px[k] = qx[k]; py[k] = qy[k]; }
+        n = m;
+    }
+    return 0.5 * fabs(dm_fan<8>(px, py, n));
+}
+
+__global__ __launch_bounds__(64 * DM_WAVES) void dota_best_kernel(const float* __restrict__ dets, const int32_t* __restrict__ num, int64_t max_det,
+                                                                  const double* __restrict__ prep, const int32_t* __restrict__ cls_off, int64_t nl,
+                                                                  int nc, const float* __restrict__ iouv, int niou, double* __restrict__ best_iou,
+                                                                  int32_t* __restrict__ best_t, int32_t* __restrict__ owner)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * DM_WAVES + (threadIdx.x >> 6);
+    if (i >= sm_count(num, max_det)) return;                          // wave-uniform
+    const float* pr = dets + i * 7;
+    const float cls = pr[6];
+    int64_t lo = 0, hi = 0;
+    if (cls >= 0.f && cls < (float)nc) {                              // NaN fails both
+        const int c = (int)cls;
+        if ((float)c == cls && c >= 0 && c < nc) {
+            lo = cls_off[c];
+            hi = cls_off[c + 1];
+            lo = lo < 0 ? 0 : (lo > nl ? nl : lo);                    // a bad table gives wrong numbers, never an access outside prep
+            hi = hi < lo ? lo : (hi > nl ? nl : hi);
+        }
+    }
+    double bi = -1.0;
+    int bt = -1;
+    if (lo < hi) {
+        double dx[4], dy[4];
+        dm_rect_corners(pr, dx, dy);
+        const bool live = dm_finite4(dx, dy);
+        double x0 = dx[0], x1 = dx[0], y0 = dy[0], y1 = dy[0];
+#pragma unroll
+        for (int k = 1; k < 4; k++) {
+            x0 = dx[k] < x0 ? dx[k] : x0; x1 = dx[k] > x1 ? dx[k] : x1;
+            y0 = dy[k] < y0 ? dy[k] : y0; y1 = dy[k] > y1 ? dy[k] : y1;
+        }
+        const double ad = 0.5 * fabs(dm_fan<4>(dx, dy, 4));
+        for (int64_t t = lo + lane; t < hi; t += 64) {
+            const double* L = prep + t * DM_PREP;
+            double v = 0.0;
+            if (live && !(x1 < L[9] || L[10] < x0 || y1 < L[11] || L[12] < y0)) {     // disjoint bounds: IoU 0, exactly
+                const double inter = dm_clip_area(dx, dy, L);
+                const double den = ad + L[8] - inter;
+                v = den <= 0.0 ? 0.0 : inter / den;
+            }
+            if (v > bi) { bi = v; bt = (int)t; }
+        }
+    }
+    // first maximum in label order: larger IoU wins, equal IoU the smaller label index, -1 (no label seen) loses to any index
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double oi = __shfl_xor(bi, o, 64);
+        const int ot = __shfl_xor(bt, o, 64);
+        if (ot >= 0 && (bt < 0 || oi > bi || (oi == bi && ot < bt))) { bi = oi; bt = ot; }
+    }
+    if (lane == 0) {
+        best_iou[i] = bi;
+        best_t[i] = bt;
+        if (bt >= 0 && bt < nl)
+            for (int k = 0; k < niou; k++)
+                if (bi > (double)iouv[k]) atomicMin(&owner[(int64_t)bt * niou + k], (int)i);
+    }
+}
+
+__global__ __launch_bounds__(256) void dota_emit_kernel(const float* __restrict__ dets, const int32_t* __restrict__ num, int64_t max_det, int64_t nl,
+                                                        const float* __restrict__ iouv, int niou, const double* __restrict__ best_iou,
+                                                        const int32_t* __restrict__ best_t, const int32_t* __restrict__ owner,
+                                                        const double* __restrict__ prep, unsigned char* __restrict__ status,
+                                                        float* __restrict__ conf, float* __restrict__ pcls, int64_t cap,
+                                                        const int64_t* __restrict__ cursor)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t n = sm_count(num, max_det);
+    if (i >= n) return;
+    const int64_t cur = *cursor;
+    if (cur < 0 || cur > cap || n > cap - cur) return;               // overflow: nothing is written (dota_advance_kernel raises the flag)
+    const int bt = best_t[i];
+    const double bi = best_iou[i];
+    const bool has = bt >= 0 && bt < nl;
+    const bool hard = has && prep[(int64_t)bt * DM_PREP + 13] != 0.0;
+    unsigned char* row = status + (cur + i) * niou;
+    for (int k = 0; k < niou; k++) {
+        unsigned char s = 0;
+        if (has && bi > (double)iouv[k]) s = hard ? 2 : (owner[(int64_t)bt * niou + k] == (int)i ? 1 : 0);
+        row[k] = s;
+    }
+    conf[cur + i] = dets[i * 7 + 5];
+    pcls[cur + i] = dets[i * 7 + 6];
+}
+
+// stream-ordered after every row is written and every read of the cursor: the cursor, the flag, and the positives of the scene's classes
+__global__ __launch_bounds__(256) void dota_advance_kernel(const int32_t* __restrict__ num, int64_t max_det, int64_t cap, int64_t* __restrict__ cursor,
+                                                           int32_t* __restrict__ overflow, const double* __restrict__ prep,
+                                                           const int32_t* __restrict__ cls_off, int64_t nl, int nc, int64_t* __restrict__ npos)
+{
+    if (blockIdx.x != 0) return;
+    const int64_t n = sm_count(num, max_det), cur = *cursor;
+    const bool fits = !(cur < 0 || cur > cap || n > cap - cur);
+    __syncthreads();                                                  // every thread has read the cursor before thread 0 moves it
+    if (fits)
+        for (int c = threadIdx.x; c < nc; c += 256) {
+            int64_t lo = cls_off[c], hi = cls_off[c + 1];
+            lo = lo < 0 ? 0 : (lo > nl ? nl : lo);
+            hi = hi < lo ? lo : (hi > nl ? nl : hi);
+            int64_t easy = 0;
+            for (int64_t t = lo; t < hi; t++) easy += prep[t * DM_PREP + 13] == 0.0 ? 1 : 0;
+            npos[c] += easy;
+        }
+    if (threadIdx.x == 0) {
+        if (fits) *cursor = cur + n;
+        else *overflow = 1;
+    }
+}
+
+extern "C" int ryolo_dota_match_workspace_bytes(int64_t max_det, int64_t nl, int niou, size_t* bytes)
+{
+    if (!bytes || max_det < 0 || nl < 0 || niou < 1 || niou > AP_MAX_T) return RY_ERR_ARG;
+    *bytes = dm_align((size_t)max_det * 8) + dm_align((size_t)max_det * 4) + dm_align((size_t)nl * DM_PREP * 8) + dm_align((size_t)nl * niou * 4) + 256;
+    return RY_OK;
+}
+
+extern "C" int ryolo_dota_match(const float* dets, const int32_t* num, int64_t max_det, const float* labels, const int32_t* cls_off, int64_t nl,
+                                int nc, const float* iouv, int niou, unsigned char* status, float* conf, float* pcls, int64_t cap, int64_t* cursor,
+                                int32_t* overflow, int64_t* npos, void* ws, size_t ws_bytes, hipStream_t stream)
+{
+    if (max_det < 0 || nl < 0 || nc < 1 || niou < 1 || cap < 0) return RY_ERR_ARG;
+    if (nc > MAP_MAX_CLASSES || niou > AP_MAX_T || max_det >= INT_MAX || nl >= INT_MAX / AP_MAX_T) return RY_ERR_UNSUPPORTED;
+    if (!cls_off || !cursor || !overflow || !npos || !num || !ws || (nl > 0 && !labels)) return RY_ERR_ARG;
+    if (max_det > 0 && (!dets || !iouv || !status || !conf || !pcls)) return RY_ERR_ARG;
+    size_t need = 0;
+    ryolo_dota_match_workspace_bytes(max_det, nl, niou, &need);
+    if (ws_bytes < need) return RY_ERR_WORKSPACE;
+    unsigned char* base = reinterpret_cast<unsigned char*>(ws);
+    double* best_iou = reinterpret_cast<double*>(base);     base += dm_align((size_t)max_det * 8);
+    int32_t* best_t = reinterpret_cast<int32_t*>(base);     base += dm_align((size_t)max_det * 4);
+    double* prep = reinterpret_cast<double*>(base);         base += dm_align((size_t)nl * DM_PREP * 8);
+    int32_t* owner = reinterpret_cast<int32_t*>(base);
+    if (nl > 0)
+        hipLaunchKernelGGL(dota_prep_kernel, dim3((unsigned)ry_cdiv(nl, 256)), dim3(256), 0, stream, labels, nl, niou, prep, owner);
+    if (max_det > 0) {
+        hipLaunchKernelGGL(dota_best_kernel, dim3((unsigned)ry_cdiv(max_det, DM_WAVES)), dim3(64 * DM_WAVES), 0, stream, dets, num, max_det, prep,
+                           cls_off, nl, nc, iouv, niou, best_iou, best_t, owner);
+        hipLaunchKernelGGL(dota_emit_kernel, dim3((unsigned)ry_cdiv(max_det, 256)), dim3(256), 0, stream, dets, num, max_det, nl, iouv, niou, best_iou,
+                           best_t, owner, prep, status, conf, pcls, cap, cursor);
+    }
+    hipLaunchKernelGGL(dota_advance_kernel, dim3(1), dim3(256), 0, stream, num, max_det, cap, cursor, overflow, prep, cls_off, nl, nc, npos);
+    RY_CHECK_LAUNCH();
+    return RY_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ VOC AP from the DOTA statistics
+// Per class and threshold: the rows of the class in confidence order (the sort of ryolo_ap_per_class), rows with status 2 left out, running
+// true / false positive counts by the ballot / popcount scans of ap_curves_kernel, then the 11-point VOC07 mean or the VOC12 area.
+__global__ __launch_bounds__(AP_THREADS) void voc_count_kernel(const float* __restrict__ pcls, int64_t n, int nc, int64_t* __restrict__ cnt,
+                                                               int64_t* __restrict__ off)
+{
+    __shared__ int c_p[MAP_MAX_CLASSES];
+    const int tid = threadIdx.x;
+    for (int k = tid; k < nc; k += AP_THREADS) c_p[k] = 0;
+    __syncthreads();
+    for (int64_t i = tid; i < n; i += AP_THREADS) {
+        const float c = pcls[i];
+        const int k = (int)c;
+        if (k >= 0 && k < nc && (float)k == c) atomicAdd(&c_p[k], 1);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int64_t run = 0;
+        for (int k = 0; k < nc; k++) { cnt[k] = c_p[k]; off[k] = run; run += c_p[k]; }
+    }
+}
+
+// grid (T, classes): recall / precision after every counted row of the class at threshold t, and how many rows were counted
+__global__ __launch_bounds__(AP_THREADS) void voc_curves_kernel(const unsigned char* __restrict__ status, const float* __restrict__ pcls,
+                                                                const int64_t* __restrict__ order, int64_t n, int T, const int64_t* __restrict__ cnt,
+                                                                const int64_t* __restrict__ npos, const int64_t* __restrict__ off,
+                                                                double* __restrict__ rec, double* __restrict__ prec, int64_t* __restrict__ used)
+{
+    __shared__ unsigned wt[16][2], wp[16][2], tot[2];
+    const int t = blockIdx.x, k = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t np_ = npos[k];
+    if (cnt[k] == 0 || np_ <= 0) { if (tid == 0) used[(int64_t)k * T + t] = 0; return; }
+    const int64_t o0 = off[k];
+    const float kc = (float)k;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    int64_t run_t = 0, run_f = 0;
+    for (int64_t i0 = 0; i0 < n; i0 += AP_THREADS) {
+        const int64_t i = i0 + tid;
+        const int64_t idx = i < n ? order[i] : 0;
+        const bool mine = i < n && pcls[idx] == kc;
+        const unsigned char s = mine ? status[idx * T + t] : 2;
+        const bool ft = s == 1, ff = s != 1 && s != 2;
+        const unsigned long long bt_ = __ballot(ft), bf_ = __ballot(ff);
+        const unsigned pt = (unsigned)__popcll(bt_ & lt), pf = (unsigned)__popcll(bf_ & lt);
+        if (lane == 0) { wt[wave][0] = (unsigned)__popcll(bt_); wt[wave][1] = (unsigned)__popcll(bf_); }
+        __syncthreads();
+        if (tid < 2) {
+            unsigned r = 0;
+            for (int w = 0; w < 16; w++) { wp[w][tid] = r; r += wt[w][tid]; }
+            tot[tid] = r;
+        }
+        __syncthreads();
+        if (ft || ff) {
+            const int64_t tpc = run_t + wp[wave][0] + pt + (ft ? 1 : 0), fpc = run_f + wp[wave][1] + pf + (ff ? 1 : 0);
+            const int64_t pos = o0 + tpc + fpc - 1;
+            rec[(int64_t)t * n + pos] = (double)tpc / (double)np_;
+            prec[(int64_t)t * n + pos] = (double)tpc / fmax((double)(tpc + fpc), 2.220446049250313e-16);
+        }
+        run_t += tot[0];
+        run_f += tot[1];
+        __syncthreads();
+    }
+    if (tid == 0) used[(int64_t)k * T + t] = run_t + run_f;
+}
+
+// grid (T, classes): metric 0 the 11-point VOC07 mean, metric 1 the VOC12 area under the precision envelope
+__global__ __launch_bounds__(AP_THREADS) void voc_integrate_kernel(int64_t n, int T, int metric, const int64_t* __restrict__ npos,
+                                                                   const int64_t* __restrict__ off, const int64_t* __restrict__ used,
+                                                                   const double* __restrict__ rec, const double* __restrict__ prec,
+                                                                   double* __restrict__ env, const double* __restrict__ grid11, double* __restrict__ ap)
+{
+    __shared__ double wmax[16][11], carry_s, term[AP_THREADS], sum_s;
+    const int t = blockIdx.x, k = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (npos[k] <= 0) { if (tid == 0) ap[(int64_t)k * T + t] = __builtin_nan(""); return; }
+    const int64_t m = used[(int64_t)k * T + t];
+    const double* r_ = rec + (int64_t)t * n + off[k];
+    const double* p_ = prec + (int64_t)t * n + off[k];
+    double* e_ = env + (int64_t)t * n + off[k];
+    if (metric == 0) {
+        double g[11], mx[11];
+#pragma unroll
+        for (int q = 0; q < 11; q++) { g[q] = grid11[q]; mx[q] = 0.0; }     // precision is never negative: 0 is also "no such row"
+        for (int64_t j = tid; j < m; j += AP_THREADS) {
+            const double r = r_[j], p = p_[j];
+#pragma unroll
+            for (int q = 0; q < 11; q++)
+                if (r >= g[q]) mx[q] = fmax(mx[q], p);
+        }
+#pragma unroll
+        for (int q = 0; q < 11; q++) {
+            double v = mx[q];
+            for (int d = 32; d > 0; d >>= 1) v = fmax(v, __shfl_xor(v, d, 64));
+            if (lane == 0) wmax[wave][q] = v;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double a = 0.0;
+            for (int q = 0; q < 11; q++) {
+                double v = 0.0;
+                for (int w = 0; w < 16; w++) v = fmax(v, wmax[w][q]);
+                a = a + v / 11.0;
+            }
+            ap[(int64_t)k * T + t] = a;
+        }
+        return;
+    }
+    if (tid == 0) { carry_s = 0.0; sum_s = 0.0; }                      // mpre ends with 0
+    __syncthreads();
+    for (int64_t hi = m; hi > 0; hi -= AP_THREADS) {                   // running maximum from the right, chunk by chunk
+        const int64_t i = hi - AP_THREADS + tid;
+        double v = i >= 0 ? p_[i] : 0.0;
+        for (int d = 1; d < 64; d <<= 1) {
+            const double o = __shfl_down(v, d, 64);
+            if (lane + d < 64) v = fmax(v, o);
+        }
+        if (lane == 0) wmax[wave][0] = v;
+        __syncthreads();
+        double later = carry_s;
+        for (int w = wave + 1; w < 16; w++) later = fmax(later, wmax[w][0]);
+        v = fmax(v, later);
+        if (i >= 0) e_[i] = v;
+        __syncthreads();
+        if (tid == 0) {
+            double c = carry_s;
+            for (int w = 0; w < 16; w++) c = fmax(c, wmax[w][0]);
+            carry_s = c;
+        }
+        __syncthreads();
+    }
+    __threadfence_block();
+    __syncthreads();
+    // sum over j of (mrec[j + 1] - mrec[j]) * mpre[j + 1], ascending, one after the other; a term where mrec does not change is +0 and
+    // leaves the sum as it is, and the last one, (1 - rec[m - 1]) * 0, likewise
+    for (int64_t j0 = 0; j0 < m; j0 += AP_THREADS) {
+        const int64_t j = j0 + tid;
+        term[tid] = j < m ? (r_[j] - (j > 0 ? r_[j - 1] : 0.0)) * e_[j] : 0.0;
+        __syncthreads();
+        if (tid == 0) {
+            double a = sum_s;
+            const int lim = (int)(m - j0 < AP_THREADS ? m - j0 : AP_THREADS);
+            for (int q = 0; q < lim; q++) a = a + term[q];
+            sum_s = a;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) ap[(int64_t)k * T + t] = sum_s;
+}
+
+extern "C" int ryolo_ap_voc_workspace_bytes(int64_t n, int niou, int nc, size_t* bytes)
+{
+    if (!bytes || n < 0 || niou < 1 || niou > AP_MAX_T || nc < 1 || nc > MAP_MAX_CLASSES) return RY_ERR_ARG;
+    size_t sort = 0;
+    if (n > 0 && ryolo_sort_workspace_bytes(1, n, &sort) != RY_OK) return RY_ERR_ARG;
+    const size_t nn = (size_t)(n > 0 ? n : 1);
+    *bytes = ap_align(sort) + ap_align(nn * 8) + ap_align((size_t)nc * 8) + ap_align((size_t)nc * niou * 8) + 3 * ap_align(nn * niou * 8);
+    return RY_OK;
+}
+
+extern "C" int ryolo_ap_voc(const unsigned char* status, const float* conf, const float* pred_cls, int64_t n, const int64_t* npos, int nc, int niou,
+                            int metric, const double* grid11, void* ws, size_t ws_bytes, double* ap, int64_t* n_pred, hipStream_t stream)
+{
+    size_t need = 0;
+    if (ryolo_ap_voc_workspace_bytes(n, niou, nc, &need) != RY_OK || (metric != 0 && metric != 1)) return RY_ERR_ARG;
+    if (n >= INT_MAX) return RY_ERR_UNSUPPORTED;
+    if (!ws || ws_bytes < need) return RY_ERR_WORKSPACE;
+    if (!ap || !n_pred || !npos || !grid11) return RY_ERR_ARG;
+    if (n > 0 && (!status || !conf || !pred_cls)) return RY_ERR_ARG;
+    size_t sort = 0;
+    if (n > 0) ryolo_sort_workspace_bytes(1, n, &sort);
+    const size_t nn = (size_t)(n > 0 ? n : 1);
+    unsigned char* base = reinterpret_cast<unsigned char*>(ws);
+    void* sort_ws = base;                              base += ap_align(sort);
+    int64_t* order = reinterpret_cast<int64_t*>(base); base += ap_align(nn * 8);
+    int64_t* off = reinterpret_cast<int64_t*>(base);   base += ap_align((size_t)nc * 8);
+    int64_t* used = reinterpret_cast<int64_t*>(base);  base += ap_align((size_t)nc * niou * 8);
+    double* rec = reinterpret_cast<double*>(base);     base += ap_align(nn * niou * 8);
+    double* prec = reinterpret_cast<double*>(base);    base += ap_align(nn * niou * 8);
+    double* env = reinterpret_cast<double*>(base);
+    if (n > 0) {
+        const int rc = ryolo_argsort_desc(conf, n, order, sort_ws, sort, stream);       // (confidence desc, index asc)
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(voc_count_kernel, dim3(1), dim3(AP_THREADS), 0, stream, pred_cls, n, nc, n_pred, off);
+    hipLaunchKernelGGL(voc_curves_kernel, dim3(niou, nc), dim3(AP_THREADS), 0, stream, status, pred_cls, order, n, niou, n_pred, npos, off, rec, prec, used);
+    hipLaunchKernelGGL(voc_integrate_kernel, dim3(niou, nc), dim3(AP_THREADS), 0, stream, n, niou, metric, npos, off, used, rec, prec, env, grid11, ap);
+    RY_CHECK_LAUNCH();
+    return RY_OK;
+}

@@ -118,6 +118,7 @@ class SceneDataset(BaseDataset):
         self.items = []                                            # (scene, rate index, x0, y0, c)
         self.last_windows, self._row_wins = [], []
         self._boxes = {}                                           # scene -> label_boxes of its labels (the cull of every use)
+        self._difficult = {}                                       # scene -> uint8 [n] "difficult" flags (scene_difficult)
 
     # ------------------------------------------------------------------ the item table
     def _pool_files(self):
@@ -129,6 +130,22 @@ class SceneDataset(BaseDataset):
         if got is None:
             got = self._labels[scene] = self._parse_label_file(self.scene_label_files[scene])
         return got
+
+    def scene_difficult(self, scene):
+        """uint8 [n] aligned with scene_labels(scene): nonzero marks a label the DOTA / VOC protocol calls difficult (lib/dota_eval.py).
+        Here: the flags given to set_arrays, else zeros; a dataset that reads them from its label files overrides _parse_difficult."""
+        got = self._difficult.get(scene)
+        if got is None:
+            n = len(self.scene_labels(scene)[1])
+            got = self._parse_difficult(scene)
+            got = np.zeros(n, dtype=np.uint8) if got is None else (np.asarray(got).reshape(-1) != 0).astype(np.uint8)
+            if len(got) != n:
+                raise ValueError(f"SceneDataset: {len(got)} difficult flags for the {n} labels of scene {scene}")
+            self._difficult[scene] = got
+        return got
+
+    def _parse_difficult(self, scene):
+        return None
 
     def _window_labels(self, scene, x0, y0, c):
         polys, cls = self.scene_labels(scene)
@@ -173,10 +190,21 @@ class SceneDataset(BaseDataset):
         self.img_files = ["{}#{},{},{}".format(self.scene_files[s], x0, y0, c) for s, _, x0, y0, c in self.items]
         self.label_files = [self.scene_label_files[s] for s, _, _, _, _ in self.items]
 
-    def set_arrays(self, images, polys, labels):
-        """Decoded scenes (uint8 HWC BGR) and their parsed labels (scene pixels) instead of files; plans the windows."""
+    def set_arrays(self, images, polys, labels, difficult=None):
+        """Decoded scenes (uint8 HWC BGR) and their parsed labels (scene pixels) instead of files; plans the windows.  difficult: per scene
+        the flags scene_difficult returns (default: none is difficult)."""
         self.img_files, self.label_files = [], []
         super().set_arrays(images, polys, labels)
+        self._difficult = {}
+        if difficult is not None:
+            difficult = list(difficult)
+            if len(difficult) != len(self._labels):
+                raise ValueError(f"SceneDataset.set_arrays: difficult flags for {len(difficult)} scenes, {len(self._labels)} scenes")
+            for i, d in enumerate(difficult):
+                d = (np.asarray(d).reshape(-1) != 0).astype(np.uint8)
+                if len(d) != len(self._labels[i][1]):
+                    raise ValueError(f"SceneDataset.set_arrays: {len(d)} difficult flags for the {len(self._labels[i][1])} labels of scene {i}")
+                self._difficult[i] = d
         self.scene_files, self.scene_label_files = list(self.img_files), list(self.img_files)
         self.plan_windows()
 
@@ -238,3 +266,9 @@ class DOTASceneDataset(SceneDataset):
         self.plan_windows()
 
     load_files = DOTADataset.load_files
+
+    def _parse_difficult(self, scene):
+        """Field 9 of every label line (the field after the category name): nonzero means difficult, an absent field 0."""
+        with open(self.scene_label_files[scene].rstrip(), "r") as fh:
+            fields = [line.split(" ") for line in fh.readlines()]
+        return np.array([1 if len(f) > 9 and f[9].strip() and float(f[9]) != 0 else 0 for f in fields], dtype=np.uint8)
