@@ -559,6 +559,41 @@ int ryolo_anchor_kmeans_workspace_bytes(int64_t n, size_t* bytes);
 int ryolo_anchor_kmeans(const float* wh, int64_t n, float* k, int K, int iters, int init, int32_t* assign, void* workspace,
                         size_t workspace_bytes, ryolo_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Object-level copy-paste for scene training (csrc/copypaste.hip; datasets/copy_paste.py).  The reference has no such
+ * stage; tests/copy_paste_ref.py restates these semantics in numpy.  No allocation, no synchronisation, capturable, deterministic.
+ * `items` = device array of np records {int64 src_off; int SH, SW, slot; float cls, quad[8]; double M[6], Minv[6]}
+ * (ryolo_paste_item_bytes = sizeof): the source label `quad` (scene pixels) of the SH x SW scene at pool + src_off, the affine map
+ * M (scene -> canvas, row major 2 x 3) and its inverse.  Items are sorted by slot, inside a slot in paste order; first int32 [B + 1]: slot b
+ * owns items[first[b] .. first[b + 1]).  Item j is VALID when 0 <= slot < B, first[slot] <= j < first[slot + 1] <= np and SH, SW > 0; it
+ * is LIVE when it is valid, its destination quad is finite and that quad's shoelace sum (sum of x_k y_k+1 - x_k+1 y_k, in vertex order,
+ * double) is not zero.  An item that is not live writes no pixel and buries no row (an item whose slot lies outside [0, B) is IGNORED
+ * in this sense, not rejected: the table is on the device and is not read back).
+ * ------------------------------------------------------------------------------------------------------------ */
+int ryolo_paste_item_bytes(int* bytes);
+/* One thread per item: dq fp32 [np][8] = the destination quad, x' = M0 x + M1 y + M2, y' = M3 x + M4 y + M5 in double, left to right,
+ * rounded to float (written for every item); bbox int32 [np][4] = (x0, y0, x1, y1), the canvas pixels x0 <= px < x1, y0 <= py < y1 with
+ * ceil(min x') <= px <= floor(max x') clipped to [0, S); all zero for an item that is not live or whose box misses the canvas. */
+int ryolo_paste_prepare(const void* items_dev, int np, const int32_t* first_dev, int B, int S, float* dq, int32_t* bbox, ryolo_stream_t stream);
+/* canvas uint8 [B][S][S][3] (BGR, the assembler's finished canvases before ryolo_to_tensor), in place.  Pixel (px, py) of canvas `slot` is
+ * INSIDE live item j when for the four edges a -> b of dq[j] promoted to double s ((bx - ax)(py - ay) - (by - ay)(px - ax)) >= 0, s = +-1
+ * the sign of the quad's shoelace sum.  A pixel takes the LAST item of its slot that it is inside: it is written once, with
+ * ryolo_warp_perspective_u8's sample for the inverse map (Minv; 0 0 1) and border 114 (taps outside the scene read 114); pixels inside
+ * no item are not touched.  Launch: a grid over (item, 32 x 8 tile of its bbox) — work follows the pasted area, not B S S; max_bw x
+ * max_bh (<= 0: the canvas) is the caller's bound on a box and only sizes the grid (an item with more tiles loops). */
+int ryolo_paste_pixels(const uint8_t* pool, const void* items_dev, int np, const int32_t* first_dev, int B, const float* dq, const int32_t* bbox,
+                       uint8_t* canvas, int S, int max_bw, int max_bh, ryolo_stream_t stream);
+/* targets [nt][10] = (slot, class, 8 coordinates), NaN rows allowed -> out [nt + np][10]: rows 0 .. nt - 1 the existing rows in order, row
+ * nt + j = (slot, cls, dq[j]) of item j; a row for an item that is not valid is (0, cls, NaN x 8).  A row is OCCLUDED by live item k of
+ * its own slot when |shoelace(clip(row, dq[k]))| / |shoelace(row)| >= occ_thr: for an existing row every item of the slot counts, for
+ * the row of item j the items k > j of the slot.  The coordinates of an occluded row become NaN (slot and class stay), which
+ * ryolo_encode_labels removes in order.  A row with a NaN coordinate or with |shoelace| <= 0 is copied as it is.  The clip is fp64
+ * Sutherland-Hodgman of the row's quad against the four half-planes of dq[k] in its edge order (0 -> 1, 1 -> 2, 2 -> 3, 3 -> 0); with
+ * d(p) the edge expression above, a vertex with d >= 0 is inside, an edge whose ends differ adds a + t (b - a), t = d(a) / (d(a) - d(b));
+ * at most 20 vertices are kept.  One thread per output row.  occ_thr > 0. */
+int ryolo_paste_labels(const float* targets, int64_t nt, const void* items_dev, int np, const int32_t* first_dev, int B, const float* dq,
+                       double occ_thr, float* out, ryolo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@
 // load_mosaic / load_mosaic9 / mixup ran); warp and hsv restate OpenCV (third-party, absent here, version un-pinned by the reference):
 // "parity unpinned" — checked only against this build's own numpy restatement (oracle/ref_data.py).
 #include "common.h"
-#include "augment_px.h"     // load_px2, area_fast_scales, hsv_lut_pixel, area_axis, ResizeItem, LabelRow
+#include "augment_px.h"     // load_px2, warp_bilinear_px, area_fast_scales, hsv_lut_pixel, area_axis, ResizeItem, LabelRow
 
 struct PasteRect {               // one `canvas[dy:dy+h, dx:dx+w] = src[sy:sy+h, sx:sx+w]`
     int64_t src_off;             // byte offset of the source image in the pool
@@ -73,51 +73,7 @@ __global__ __launch_bounds__(256) void warp_perspective_kernel(const uint8_t* __
     const int b = blockIdx.z, y = blockIdx.y;
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= DW) return;
-    const double* m = Minv + (int64_t)b * 9;
-    // cv::warpPerspective: W = M20 x + M21 y + M22; fX = (M00 x + M01 y + M02) / W scaled by INTER_TAB_SIZE = 32 and rounded
-    // (saturate_cast<int> of a double = cvRound: round half to even)
-    double W = m[6] * x + m[7] * y + m[8];
-    W = W ? 32.0 / W : 0.0;
-    const double fX = fmax((double)INT_MIN, fmin((double)INT_MAX, (m[0] * x + m[1] * y + m[2]) * W));
-    const double fY = fmax((double)INT_MIN, fmin((double)INT_MAX, (m[3] * x + m[4] * y + m[5]) * W));
-    const int X = (int)rint(fX), Y = (int)rint(fY);
-    const int sx = X >> 5, sy = Y >> 5, ax = X & 31, ay = Y & 31;
-    // bilinear weights: OpenCV's table holds (1 - a/32, a/32) products scaled by 2^15 and rounded, corrected so the four sum to 2^15
-    const float fx1 = ax * (1.f / 32.f), fy1 = ay * (1.f / 32.f);
-    const float wf[4] = {(1.f - fy1) * (1.f - fx1), (1.f - fy1) * fx1, fy1 * (1.f - fx1), fy1 * fx1};
-    int w[4], sum = 0, imax = 0, imin = 0;
-    for (int k = 0; k < 4; k++) {
-        w[k] = (int)rintf(wf[k] * 32768.f);
-        sum += w[k];
-        if (w[k] > w[imax]) imax = k;
-        if (w[k] < w[imin]) imin = k;
-    }
-    // (initInterTab2D: the rounding error of the sum is pushed into the largest / smallest weight)
-    if (sum != 32768) {
-        const int diff = sum - 32768;
-        if (diff < 0) w[imax] -= diff; else w[imin] -= diff;
-    }
-    const uint8_t* sb = src + (int64_t)b * SH * SW * 3;
-    uint8_t* d = dst + (((int64_t)b * DH + y) * DW + x) * 3;
-    if (sx >= 0 && sx + 1 < SW && sy >= 0 && sy + 1 < SH && (int64_t)(sy + 1) * SW + sx + 3 <= (int64_t)SH * SW) {
-        // all four taps inside the image (and 8 readable bytes behind the lower pair): the same integer sums from two 8-byte loads
-        const unsigned long long r0 = load_px2(sb + ((int64_t)sy * SW + sx) * 3), r1 = load_px2(sb + ((int64_t)(sy + 1) * SW + sx) * 3);
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const int acc = px2_byte(r0, c) * w[0] + px2_byte(r0, c + 3) * w[1] + px2_byte(r1, c) * w[2] + px2_byte(r1, c + 3) * w[3];
-            d[c] = (uint8_t)((acc + (1 << 14)) >> 15);
-        }
-        return;
-    }
-    for (int c = 0; c < 3; c++) {
-        int acc = 0;
-        for (int k = 0; k < 4; k++) {
-            const int px = sx + (k & 1), py = sy + (k >> 1);
-            const int v = ((unsigned)px < (unsigned)SW && (unsigned)py < (unsigned)SH) ? sb[((int64_t)py * SW + px) * 3 + c] : border;
-            acc += v * w[k];
-        }
-        d[c] = (uint8_t)((acc + (1 << 14)) >> 15);
-    }
+    warp_bilinear_px(src + (int64_t)b * SH * SW * 3, SH, SW, Minv + (int64_t)b * 9, x, y, border, dst + (((int64_t)b * DH + y) * DW + x) * 3);
 }
 
 // cv2.cvtColor(BGR2HSV) on uint8 -> LUTs -> cv2.cvtColor(HSV2BGR), in place (lib/augmentations.py:8-21).  lut [3][256] uint8.

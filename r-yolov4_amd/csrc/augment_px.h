@@ -14,6 +14,55 @@ __device__ __forceinline__ unsigned long long load_px2(const uint8_t* p)
 }
 __device__ __forceinline__ int px2_byte(unsigned long long v, int k) { return (int)((v >> (8 * k)) & 255ull); }
 
+// One destination pixel (x, y) of cv::warpPerspective with INTER_LINEAR and a constant border: m = the INVERSE map as 9 doubles, sb the
+// SH x SW source, d the 3 bytes of the result.  warp_perspective_kernel (augment.hip) and paste_pixels_kernel (copypaste.hip) are this.
+__device__ __forceinline__ void warp_bilinear_px(const uint8_t* __restrict__ sb, int SH, int SW, const double* __restrict__ m, int x, int y, int border,
+                                                 uint8_t* __restrict__ d)
+{
+    // cv::warpPerspective: W = M20 x + M21 y + M22; fX = (M00 x + M01 y + M02) / W scaled by INTER_TAB_SIZE = 32 and rounded
+    // (saturate_cast<int> of a double = cvRound: round half to even)
+    double W = m[6] * x + m[7] * y + m[8];
+    W = W ? 32.0 / W : 0.0;
+    const double fX = fmax((double)INT_MIN, fmin((double)INT_MAX, (m[0] * x + m[1] * y + m[2]) * W));
+    const double fY = fmax((double)INT_MIN, fmin((double)INT_MAX, (m[3] * x + m[4] * y + m[5]) * W));
+    const int X = (int)rint(fX), Y = (int)rint(fY);
+    const int sx = X >> 5, sy = Y >> 5, ax = X & 31, ay = Y & 31;
+    // bilinear weights: OpenCV's table holds (1 - a/32, a/32) products scaled by 2^15 and rounded, corrected so the four sum to 2^15
+    const float fx1 = ax * (1.f / 32.f), fy1 = ay * (1.f / 32.f);
+    const float wf[4] = {(1.f - fy1) * (1.f - fx1), (1.f - fy1) * fx1, fy1 * (1.f - fx1), fy1 * fx1};
+    int w[4], sum = 0, imax = 0, imin = 0;
+    for (int k = 0; k < 4; k++) {
+        w[k] = (int)rintf(wf[k] * 32768.f);
+        sum += w[k];
+        if (w[k] > w[imax]) imax = k;
+        if (w[k] < w[imin]) imin = k;
+    }
+    // (initInterTab2D: the rounding error of the sum is pushed into the largest / smallest weight)
+    if (sum != 32768) {
+        const int diff = sum - 32768;
+        if (diff < 0) w[imax] -= diff; else w[imin] -= diff;
+    }
+    if (sx >= 0 && sx + 1 < SW && sy >= 0 && sy + 1 < SH && (int64_t)(sy + 1) * SW + sx + 3 <= (int64_t)SH * SW) {
+        // all four taps inside the image (and 8 readable bytes behind the lower pair): the same integer sums from two 8-byte loads
+        const unsigned long long r0 = load_px2(sb + ((int64_t)sy * SW + sx) * 3), r1 = load_px2(sb + ((int64_t)(sy + 1) * SW + sx) * 3);
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const int acc = px2_byte(r0, c) * w[0] + px2_byte(r0, c + 3) * w[1] + px2_byte(r1, c) * w[2] + px2_byte(r1, c + 3) * w[3];
+            d[c] = (uint8_t)((acc + (1 << 14)) >> 15);
+        }
+        return;
+    }
+    for (int c = 0; c < 3; c++) {
+        int acc = 0;
+        for (int k = 0; k < 4; k++) {
+            const int px = sx + (k & 1), py = sy + (k >> 1);
+            const int v = ((unsigned)px < (unsigned)SW && (unsigned)py < (unsigned)SH) ? sb[((int64_t)py * SW + px) * 3 + c] : border;
+            acc += v * w[k];
+        }
+        d[c] = (uint8_t)((acc + (1 << 14)) >> 15);
+    }
+}
+
 // cv::resize's whole-number test (`is_area_fast`, imgproc/src/resize.cpp): scale = 1 / ((double) dst / src) per axis, iscale = saturate_cast<int>
 // (round half even); both |scale - iscale| < DBL_EPSILON.  INTER_AREA downscales by whole numbers take the integer block sum, and INTER_LINEAR
 // at exactly 2 x 2 is switched to that path by OpenCV itself.  ix = iy = 0: generic path.

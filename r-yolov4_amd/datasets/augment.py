@@ -11,6 +11,7 @@ the whole batch, one launch per stage (csrc/augment.hip):
     warp_perspective   random_warping's cv2.warpPerspective, one matrix per canvas               (lib/augmentations.py:45-65)
     mixup              uint8(a r + b (1 - r))                                                    (lib/augmentations.py:24-28)
     label_stage        load_target / mosaic crop / vertex warp of every label row, element-wise   (:188-222,318-330; :67-74)
+    paste_objects      object-level copy-paste onto the finished canvases (this project's, csrc/copypaste.hip; datasets/copy_paste.py)
 
 A mosaic placement is data, not code: image i of a 4-mosaic hangs on the mosaic centre by one of its corners (MOSAIC4_CORNER), image i
 of a 9-mosaic sits at an origin that is a fixed integer combination of the sizes of the first, the previous and the current image
@@ -304,6 +305,11 @@ class _WindowItem(ctypes.Structure):      # csrc/scene.hip: _ResizeItem of a win
                 ("c", _I), ("pad_", _I)]
 
 
+class _PasteItem(ctypes.Structure):       # csrc/copypaste.hip: one pasted object (PASTE_ITEM_DTYPE is the same record for numpy)
+    _fields_ = [("src_off", _L), ("SH", _I), ("SW", _I), ("slot", _I), ("cls", ctypes.c_float), ("quad", ctypes.c_float * 8),
+                ("M", ctypes.c_double * 6), ("Minv", ctypes.c_double * 6)]
+
+
 class _LabelRow(ctypes.Structure):
     _fields_ = [("poly", ctypes.c_float * 8), ("cls", ctypes.c_float), ("slot", _I), ("w0", ctypes.c_float), ("h0", ctypes.c_float),
                 ("w1", ctypes.c_float), ("h1", ctypes.c_float), ("bx1", ctypes.c_float), ("bx2", ctypes.c_float), ("by1", ctypes.c_float),
@@ -315,6 +321,8 @@ LABEL_ROW_DTYPE = np.dtype([("poly", np.float32, 8), ("cls", np.float32), ("slot
                             ("w1", np.float32), ("h1", np.float32), ("bx1", np.float32), ("bx2", np.float32), ("by1", np.float32),
                             ("by2", np.float32), ("padw", np.float32), ("padh", np.float32), ("cx1", np.float32), ("cx2", np.float32),
                             ("cy1", np.float32), ("cy2", np.float32), ("mat", np.int32)])
+PASTE_ITEM_DTYPE = np.dtype([("src_off", np.int64), ("SH", np.int32), ("SW", np.int32), ("slot", np.int32), ("cls", np.float32),
+                             ("quad", np.float32, 8), ("M", np.float64, 6), ("Minv", np.float64, 6)])
 INTERP_LINEAR, INTERP_AREA, INTERP_COPY = 0, 1, 2
 _checked = False
 
@@ -325,12 +333,14 @@ def _check_layouts():
         return
     n = _I()
     for name, t in (("ryolo_paste_rect_bytes", _Rect), ("ryolo_resize_item_bytes", _ResizeItem), ("ryolo_label_row_bytes", _LabelRow),
-                    ("ryolo_window_item_bytes", _WindowItem)):
+                    ("ryolo_window_item_bytes", _WindowItem), ("ryolo_paste_item_bytes", _PasteItem)):
         hip.call(name, n)
         if n.value != ctypes.sizeof(t):
             raise RuntimeError(f"ryolov4_amd: struct layout mismatch for {t.__name__}: C {n.value} vs ctypes {ctypes.sizeof(t)}")
     if LABEL_ROW_DTYPE.itemsize != ctypes.sizeof(_LabelRow):
         raise RuntimeError("ryolov4_amd: LABEL_ROW_DTYPE drifted from LabelRow")
+    if PASTE_ITEM_DTYPE.itemsize != ctypes.sizeof(_PasteItem):
+        raise RuntimeError("ryolov4_amd: PASTE_ITEM_DTYPE drifted from PasteItem")
     _checked = True
 
 
@@ -421,6 +431,77 @@ def resize_hsv_windows(pool, items, luts=None):
         hip.call("ryolo_resize_hsv_windows", hip.ptr(pool.buf), hip.ptr(_to_device(arr, dev)), len(items), maxpix, hip.ptr(lt), hip.ptr(stage),
                  hip.stream())
     return stage, offs
+
+
+# ------------------------------------------------------------------------------------------------ copy-paste (csrc/copypaste.hip)
+class PasteTable:
+    """The item table of one batch on the device: `items` (PASTE_ITEM_DTYPE, sorted by slot, inside a slot in paste order), the grouping
+    table first [B + 1], and the two arrays ryolo_paste_prepare fills: dq float32 [np, 8] (destination quads) and bbox int32 [np, 4]."""
+
+    def __init__(self, items, B, device):
+        _check_layouts()
+        items = np.ascontiguousarray(items, dtype=PASTE_ITEM_DTYPE).reshape(-1)
+        slots = items["slot"].astype(np.int64)
+        if len(slots) > 1 and (np.diff(slots) < 0).any():
+            raise ValueError("PasteTable: items must be sorted by slot")
+        self.n, self.B, self.device = len(items), int(B), torch.device(device)
+        # (a slot outside [0, B) lands before first[0] or behind first[B]: in no group, so the kernels ignore the item)
+        self.first_host = np.searchsorted(slots, np.arange(self.B + 1)).astype(np.int32)
+        self.items = _to_device(np.frombuffer(items.tobytes(), dtype=np.uint8), device) if self.n else None
+        self.first = _to_device(self.first_host, device)
+        self.dq = torch.empty((self.n, 8), dtype=torch.float32, device=device)
+        self.bbox = torch.empty((self.n, 4), dtype=torch.int32, device=device)
+        # host bound on a bounding box (float64; + 2 covers the rounding to fp32 and the ceil / floor): sizes the pixel grid only
+        self.max_box = (0, 0)
+        if self.n:
+            q, M = items["quad"].astype(np.float64), items["M"]
+            xs = M[:, 0:1] * q[:, 0::2] + M[:, 1:2] * q[:, 1::2] + M[:, 2:3]
+            ys = M[:, 3:4] * q[:, 0::2] + M[:, 4:5] * q[:, 1::2] + M[:, 5:6]
+            with np.errstate(invalid="ignore"):
+                w, h = np.nan_to_num(xs.max(1) - xs.min(1), nan=0.0, posinf=2.0**30), np.nan_to_num(ys.max(1) - ys.min(1), nan=0.0, posinf=2.0**30)
+            self.max_box = (int(min(w.max(), 2.0**30)) + 2, int(min(h.max(), 2.0**30)) + 2)
+
+
+def paste_prepare(table, S):
+    """Fills table.dq / table.bbox for canvases of side S (ryolo_paste_prepare)."""
+    hip.call("ryolo_paste_prepare", hip.ptr(table.items), table.n, hip.ptr(table.first), table.B, int(S), hip.ptr(table.dq) if table.n else None,
+             hip.ptr(table.bbox) if table.n else None, hip.stream())
+    return table
+
+
+def paste_pixels(pool, table, final):
+    """In place on final uint8 [B, S, S, 3]: every pixel inside an item's destination quad takes the last such item of its slot, sampled
+    from the item's scene (pool.buf + src_off; an ImagePool or its anchor tensor) by warp_perspective's rule with border 114
+    (ryolo_paste_pixels)."""
+    hip.require_device(final, "paste_pixels")
+    pool_buf = pool.buf if isinstance(pool, ImagePool) else pool
+    if final.dtype != torch.uint8 or final.dim() != 4 or final.shape[0] != table.B or final.shape[1] != final.shape[2] or final.shape[3] != 3:
+        raise RuntimeError("paste_pixels: canvases must be uint8 [B, S, S, 3] with B the table's slot count")
+    hip.call("ryolo_paste_pixels", hip.ptr(pool_buf), hip.ptr(table.items), table.n, hip.ptr(table.first), table.B, hip.ptr(table.dq) if table.n else None,
+             hip.ptr(table.bbox) if table.n else None, hip.ptr(final), final.shape[1], table.max_box[0], table.max_box[1], hip.stream())
+    return final
+
+
+def paste_labels(table, targets10, occ_thr):
+    """targets10 [nt, 10] -> [nt + np, 10]: the existing rows in order, then one row per item; rows that a later-drawn item of their slot
+    covers by the share occ_thr or more get NaN coordinates (ryolo_paste_labels)."""
+    nt = int(targets10.shape[0])
+    tg = targets10.to(dtype=torch.float32).contiguous()
+    out = torch.empty((nt + table.n, 10), dtype=torch.float32, device=table.device)
+    hip.call("ryolo_paste_labels", hip.ptr(tg) if nt else None, nt, hip.ptr(table.items), table.n, hip.ptr(table.first), table.B,
+             hip.ptr(table.dq) if table.n else None, float(occ_thr), hip.ptr(out) if nt + table.n else None, hip.stream())
+    return out
+
+
+def paste_objects(pool, final, targets10, items, occ_thr=0.5):
+    """The three stages for one batch: items (PASTE_ITEM_DTYPE) pasted onto final [B, S, S, 3] in place, their rows appended to targets10.
+    Returns (final, targets10 [nt + np, 10], PasteTable).  No item: nothing is launched and both arguments come back as they are."""
+    table = PasteTable(items, final.shape[0], final.device)
+    if not table.n:
+        return final, targets10, table
+    paste_prepare(table, final.shape[1])
+    paste_pixels(pool, table, final)
+    return final, paste_labels(table, targets10, occ_thr), table
 
 
 def upload_label_rows(rows, device):

@@ -231,6 +231,11 @@ class BaseDataset:
         ryolo_label_stage."""
         return A.upload_label_rows(rows, self.device)
 
+    def _canvas_stage(self, final, targets10, indices):
+        """The finished uint8 canvases [B, S, S, 3] and their targets10 rows, before the flips, to_tensor and encode_labels: called once
+        per batch; returns both (SceneDataset pastes objects here: datasets/copy_paste.py)."""
+        return final, targets10
+
     # ------------------------------------------------------------------ the draws, in the reference's order
     def _load_image_plan(self, index, items, luts):
         """load_image (base_dataset.py:170-186) as a table row: resized size, interpolation, the hsv tables of this use.
@@ -365,6 +370,7 @@ class BaseDataset:
         # (mixup appends the second canvas' labels behind the first's: canvases of one sample are adjacent and in that order; samples are
         # in slot order, so the rows are already ordered the way collate_fn's torch.cat orders them)
         targets10 = A.label_stage_table(self._label_table(rows) if len(rows) else None, len(rows), np.stack(mats) if mats else None, dev)
+        final, targets10 = self._canvas_stage(final, targets10, indices)
         imgs, targets = finalize_batch(final, targets10, A._to_device(flags, dev), self.csl)
         return [self.img_files[i] for i in indices], imgs, targets
 

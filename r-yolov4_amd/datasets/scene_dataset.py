@@ -23,6 +23,7 @@ import numpy as np
 
 from . import augment as A
 from .base_dataset import BaseDataset
+from .copy_paste import CopyPaste, strictly_convex
 from .DOTA_dataset import DOTADataset
 from ..lib.tiled import axis_starts
 
@@ -98,10 +99,14 @@ class SceneDataset(BaseDataset):
     of its area lies inside.  keep_empty=False: planned windows that keep no label are not items (one launch of ryolo_scene_label_rows over
     all scenes at construction, label files only — no pixels are decoded).  jitter (default: augment): every USE of an item, mosaic
     partners included, redraws the window origin (jitter_window) from random.Random(window_seed) — never from `rng`, whose draws stay in
-    the reference's order.  `last_windows`: (item, scene, x0, y0, c) per row of the last batch's resize table."""
+    the reference's order.  `last_windows`: (item, scene, x0, y0, c) per row of the last batch's resize table.
+
+    copy_paste (a CopyPaste or a dict of its arguments; default None: off): with augment, labelled objects of the scenes the batch reads
+    are pasted onto the finished canvases and their labels appended behind the batch's rows (datasets/copy_paste.py); `last_pastes`:
+    (slot, scene, label index, angle, scale, (cx, cy)) per pasted object of the last batch.  label_table() never pastes."""
 
     def __init__(self, hyp, img_size, augment, csl, normalized_labels=False, overlap=200, rates=(1.0,), iof_thr=0.7, keep_empty=False,
-                 jitter=None, p_object=0.5, window_seed=0, **device_kw):
+                 jitter=None, p_object=0.5, window_seed=0, copy_paste=None, **device_kw):
         super().__init__(hyp, img_size, augment, csl, normalized_labels, **device_kw)
         if normalized_labels:
             raise ValueError("SceneDataset: scene labels are in scene pixels (normalized_labels=False)")
@@ -119,6 +124,12 @@ class SceneDataset(BaseDataset):
         self.last_windows, self._row_wins = [], []
         self._boxes = {}                                           # scene -> label_boxes of its labels (the cull of every use)
         self._difficult = {}                                       # scene -> uint8 [n] "difficult" flags (scene_difficult)
+        if copy_paste is not None and not isinstance(copy_paste, CopyPaste):
+            copy_paste = CopyPaste(**dict(copy_paste))
+        self.copy_paste = copy_paste
+        self.last_pastes = []
+        self._paste_sources = {}                                   # scene -> indices of its labels that can be pasted
+        self._class_counts = None                                  # class -> label count over all scenes
 
     # ------------------------------------------------------------------ the item table
     def _pool_files(self):
@@ -195,7 +206,7 @@ class SceneDataset(BaseDataset):
         the flags scene_difficult returns (default: none is difficult)."""
         self.img_files, self.label_files = [], []
         super().set_arrays(images, polys, labels)
-        self._difficult = {}
+        self._difficult, self._paste_sources, self._class_counts = {}, {}, None
         if difficult is not None:
             difficult = list(difficult)
             if len(difficult) != len(self._labels):
@@ -243,6 +254,43 @@ class SceneDataset(BaseDataset):
     def assemble_batch(self, indices):
         self.last_windows, self._row_wins = [], []
         return super().assemble_batch(indices)
+
+    # ------------------------------------------------------------------ copy-paste on the finished canvases
+    def class_counts(self):
+        """{class: number of labels over ALL scenes}, from the label files, once."""
+        if self._class_counts is None:
+            counts = {}
+            for s in range(len(self.scene_files)):
+                for c in self.scene_labels(s)[1].tolist():
+                    counts[c] = counts.get(c, 0) + 1
+            self._class_counts = counts
+        return self._class_counts
+
+    def paste_bank(self, scenes):
+        """{class: [(scene, label index, quad)]} over `scenes` ascending, labels in file order, strictly convex finite quads only."""
+        bank = {}
+        for s in sorted(set(int(v) for v in scenes)):
+            polys, cls = self.scene_labels(s)
+            src = self._paste_sources.get(s)
+            if src is None:
+                src = self._paste_sources[s] = [i for i in range(len(cls)) if strictly_convex(polys[i])]
+            for i in src:
+                bank.setdefault(float(cls[i]), []).append((s, i, polys[i]))
+        return bank
+
+    def _canvas_stage(self, final, targets10, indices):
+        self.last_pastes = []
+        cp = self.copy_paste
+        if cp is None or not self.augment:
+            return final, targets10
+        S = self.img_size
+        drawn = cp.draw(len(indices), S, self.paste_bank(w[1] for w in self.last_windows), self.class_counts(),
+                        [S / self.items[i][4] for i in indices])
+        self.last_pastes = [(slot, scene, label, angle, sc, (cx, cy)) for slot, scene, label, _, _, angle, sc, cx, cy in drawn]
+        if not drawn:
+            return final, targets10
+        final, targets10, _ = A.paste_objects(self._pool, final, targets10, cp.items(drawn, self._pool), cp.occ_thr)
+        return final, targets10
 
     def _label_chunk(self, indices):
         """BaseDataset._label_chunk over the PLANNED windows: jitter is off for its duration (the window generator is not touched) and the

@@ -68,6 +68,10 @@ _SIGNATURES = {
     "ryolo_anchor_evolve": [_P, _L, _P, _I, _P, _I, _I, ctypes.c_double, _P, _Z, _P, _P],
     "ryolo_anchor_kmeans_workspace_bytes": [_L, ctypes.POINTER(_Z)],
     "ryolo_anchor_kmeans": [_P, _L, _P, _I, _I, _I, _P, _P, _Z, _P],
+    "ryolo_paste_item_bytes": [ctypes.POINTER(_I)],
+    "ryolo_paste_prepare": [_P, _I, _P, _I, _I, _P, _P, _P],
+    "ryolo_paste_pixels": [_P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P],
+    "ryolo_paste_labels": [_P, _L, _P, _I, _P, _I, _P, ctypes.c_double, _P, _P],
 }
 _lib = None
 
