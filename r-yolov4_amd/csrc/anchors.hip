@@ -25,8 +25,6 @@
 extern "C" int ryolo_sort_workspace_bytes(int rows, int64_t n_sorted, size_t* bytes);
 extern "C" int ryolo_argsort_desc(const float* scores, int64_t N, int64_t* order, void* ws, size_t ws_bytes, hipStream_t stream);
 
-static inline size_t an_al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // ------------------------------------------------------------------------------------------------ reach
 // csrc/loss.hip, cand_test: gw = tg[4] * fg, rw = gw / aw, max(rw, 1 / rw) < 4 on both sides; modes != 0 also |cos(theta - anchor angle)| >
 // 0.866.  The image index is not looked at (the loss drops rows whose index is outside the batch).
@@ -215,7 +213,7 @@ static int an_score(const float* wh, int64_t n, const float* k, const float* v, 
 extern "C" int ryolo_anchor_workspace_bytes(int64_t n, size_t* bytes)
 {
     if (!bytes || n < 1) return RY_ERR_ARG;
-    *bytes = an_al256((size_t)AN_BLOCKS * AN_MAX_C * sizeof(AnPart));
+    *bytes = ry_align256((size_t)AN_BLOCKS * AN_MAX_C * sizeof(AnPart));
     return RY_OK;
 }
 
@@ -352,10 +350,10 @@ static int km_layout(int64_t n, size_t* part_off, size_t* area_off, size_t* orde
     const int rc = ryolo_sort_workspace_bytes(1, n, &sb);
     if (rc != RY_OK) return rc;
     size_t off = 0;
-    *part_off = off; off += an_al256((size_t)AN_BLOCKS * AN_MAX_K * sizeof(KmPart));
-    *area_off = off; off += an_al256((size_t)n * sizeof(float));
-    *order_off = off; off += an_al256((size_t)n * sizeof(int64_t));
-    *sort_off = off; off += an_al256(sb);
+    *part_off = off; off += ry_align256((size_t)AN_BLOCKS * AN_MAX_K * sizeof(KmPart));
+    *area_off = off; off += ry_align256((size_t)n * sizeof(float));
+    *order_off = off; off += ry_align256((size_t)n * sizeof(int64_t));
+    *sort_off = off; off += ry_align256(sb);
     *sort_bytes = sb;
     *total = off;
     return RY_OK;

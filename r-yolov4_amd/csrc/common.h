@@ -17,6 +17,7 @@
     } while (0)
 
 static inline int64_t ry_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+static inline size_t ry_align256(size_t x) { return (x + 255) & ~(size_t)255; }     // workspaces are carved in 256-byte steps
 
 // Environment knobs (docs/KNOBS.md): atoi of the variable, `d` when it is unset; every site keeps the value in a function-local
 // `static const`, so a knob is read once per process.

@@ -94,8 +94,11 @@ extern "C" int ryolo_map_match(float* preds, const int64_t* pred_off, const floa
 #define AP_MAX_T 16
 #define AP_THREADS 1024
 
-__global__ __launch_bounds__(AP_THREADS) void ap_count_kernel(const float* __restrict__ pcls, int64_t n, const float* __restrict__ tcls, int64_t nl, int nc,
-                                                              int64_t* __restrict__ cnt, int64_t* __restrict__ nlab, int64_t* __restrict__ off)
+// rows per class (cnt), where each class's rows start once they are grouped (off) and, for a caller with target classes, labels per class
+// (nlab; the VOC back end has none: nl = 0 and nlab null).  Both AP back ends start here.
+__global__ __launch_bounds__(AP_THREADS) void class_hist_kernel(const float* __restrict__ pcls, int64_t n, const float* __restrict__ tcls, int64_t nl,
+                                                                int nc, int64_t* __restrict__ cnt, int64_t* __restrict__ nlab,
+                                                                int64_t* __restrict__ off)
 {
     __shared__ int c_p[MAP_MAX_CLASSES], c_l[MAP_MAX_CLASSES];
     const int tid = threadIdx.x;
@@ -112,9 +115,11 @@ __global__ __launch_bounds__(AP_THREADS) void ap_count_kernel(const float* __res
         if (k >= 0 && k < nc && (float)k == c) atomicAdd(&c_l[k], 1);
     }
     __syncthreads();
+    if (nlab)
+        for (int k = tid; k < nc; k += AP_THREADS) nlab[k] = c_l[k];
     if (tid == 0) {
         int64_t run = 0;
-        for (int k = 0; k < nc; k++) { cnt[k] = c_p[k]; nlab[k] = c_l[k]; off[k] = run; run += c_p[k]; }
+        for (int k = 0; k < nc; k++) { cnt[k] = c_p[k]; off[k] = run; run += c_p[k]; }
     }
 }
 
@@ -215,20 +220,14 @@ __device__ __forceinline__ double np_pairwise_sum(const double* a, int n)
     return res;
 }
 
-// grid (T, classes): precision envelope (running maximum from the right), 101-point interpolation, trapezoid
-__global__ __launch_bounds__(AP_THREADS) void ap_integrate_kernel(int64_t n, int T, const int64_t* __restrict__ cnt, const int64_t* __restrict__ nlab,
-                                                                  const int64_t* __restrict__ off, const double* __restrict__ rec,
-                                                                  const double* __restrict__ prec, double* __restrict__ env,
-                                                                  const double* __restrict__ grid101, double* __restrict__ ap)
+// The precision envelope of one class at one threshold, by the whole workgroup: e_[i] = max(p_[i], .., p_[m - 1], 0), the running maximum
+// from the right, in chunks of AP_THREADS from the right end.  Returns the maximum over all m (0 when m == 0); e_ is visible to every
+// thread on return.
+__device__ __forceinline__ double suffix_max_envelope(const double* __restrict__ p_, double* __restrict__ e_, int64_t m)
 {
-    __shared__ double wmax[16], carry_s, y[101], term[100];
-    const int t = blockIdx.x, k = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t m = cnt[k];
-    if (m == 0 || nlab[k] == 0) { if (tid == 0) ap[(int64_t)k * T + t] = 0.0; return; }
-    const double* r_ = rec + (int64_t)t * n + off[k];
-    const double* p_ = prec + (int64_t)t * n + off[k];
-    double* e_ = env + (int64_t)t * n + off[k];
-    if (tid == 0) carry_s = 0.0;                                   // the appended knot (recall[-1] + 0.01, precision 0)
+    __shared__ double wmax[16], carry_s;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) carry_s = 0.0;                                     // precision right of the last row: the appended knot / mpre's final 0
     __syncthreads();
     for (int64_t hi = m; hi > 0; hi -= AP_THREADS) {               // chunks from the right end
         const int64_t i = hi - AP_THREADS + tid;                   // this chunk covers [hi - 1024, hi)
@@ -253,7 +252,23 @@ __global__ __launch_bounds__(AP_THREADS) void ap_integrate_kernel(int64_t n, int
     }
     __threadfence_block();
     __syncthreads();
-    const double env0 = fmax(1.0, carry_s);                        // leading knot (recall 0, precision 1)
+    return carry_s;
+}
+
+// grid (T, classes): precision envelope, 101-point interpolation, trapezoid
+__global__ __launch_bounds__(AP_THREADS) void ap_integrate_kernel(int64_t n, int T, const int64_t* __restrict__ cnt, const int64_t* __restrict__ nlab,
+                                                                  const int64_t* __restrict__ off, const double* __restrict__ rec,
+                                                                  const double* __restrict__ prec, double* __restrict__ env,
+                                                                  const double* __restrict__ grid101, double* __restrict__ ap)
+{
+    __shared__ double y[101], term[100];
+    const int t = blockIdx.x, k = blockIdx.y, tid = threadIdx.x;
+    const int64_t m = cnt[k];
+    if (m == 0 || nlab[k] == 0) { if (tid == 0) ap[(int64_t)k * T + t] = 0.0; return; }
+    const double* r_ = rec + (int64_t)t * n + off[k];
+    const double* p_ = prec + (int64_t)t * n + off[k];
+    double* e_ = env + (int64_t)t * n + off[k];
+    const double env0 = fmax(1.0, suffix_max_envelope(p_, e_, m));                        // leading knot (recall 0, precision 1)
     const double rlast = r_[m - 1] + 0.01;
     auto xp = [&](int64_t j) -> double { return j == 0 ? 0.0 : (j <= m ? r_[j - 1] : rlast); };
     auto fp = [&](int64_t j) -> double { return j == 0 ? env0 : (j <= m ? e_[j - 1] : 0.0); };
@@ -291,18 +306,46 @@ __global__ __launch_bounds__(AP_THREADS) void ap_pr_kernel(int64_t n, const int6
     }
 }
 
-static inline size_t ap_align(size_t x) { return (x + 255) & ~(size_t)255; }
+// every workspace of this file is carved front to back in 256-byte steps
+template <class T>
+static inline T* ws_take(unsigned char*& base, size_t bytes)
+{
+    T* p = reinterpret_cast<T*>(base);
+    base += ry_align256(bytes);
+    return p;
+}
 
 extern "C" int ryolo_sort_workspace_bytes(int batch, int64_t n, size_t* bytes);
 extern "C" int ryolo_argsort_desc(const float* scores, int64_t N, int64_t* order, void* ws, size_t ws_bytes, hipStream_t stream);
 
-extern "C" int ryolo_ap_workspace_bytes(int64_t n, int niou, int nc, size_t* bytes)
+static inline size_t ap_rows(int64_t n) { return (size_t)(n > 0 ? n : 1); }
+
+// Both AP workspaces begin  sort workspace | order [n]:  the size checks and the bytes of that head ...
+static int ap_head_bytes(int64_t n, int niou, int nc, size_t* head)
 {
-    if (!bytes || n < 0 || niou < 1 || niou > AP_MAX_T || nc < 1 || nc > MAP_MAX_CLASSES) return RY_ERR_ARG;
+    if (n < 0 || niou < 1 || niou > AP_MAX_T || nc < 1 || nc > MAP_MAX_CLASSES) return RY_ERR_ARG;
     size_t sort = 0;
     if (n > 0 && ryolo_sort_workspace_bytes(1, n, &sort) != RY_OK) return RY_ERR_ARG;
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    *bytes = ap_align(sort) + ap_align(nn * 8) + ap_align((size_t)3 * nc * 8) + ap_align(nn * 8) + 3 * ap_align(nn * niou * 8);
+    *head = ry_align256(sort) + ry_align256(ap_rows(n) * 8);
+    return RY_OK;
+}
+
+// ... and its carve, with the sort that fills `order`: (confidence desc, index asc), np.argsort(-conf) with ties fixed
+static int ap_sorted_order(const float* conf, int64_t n, unsigned char*& base, int64_t*& order, hipStream_t stream)
+{
+    size_t sort = 0;
+    if (n > 0) ryolo_sort_workspace_bytes(1, n, &sort);
+    void* sort_ws = ws_take<unsigned char>(base, sort);
+    order = ws_take<int64_t>(base, ap_rows(n) * 8);
+    return n > 0 ? ryolo_argsort_desc(conf, n, order, sort_ws, sort, stream) : RY_OK;
+}
+
+extern "C" int ryolo_ap_workspace_bytes(int64_t n, int niou, int nc, size_t* bytes)
+{
+    size_t head = 0;
+    if (!bytes || ap_head_bytes(n, niou, nc, &head) != RY_OK) return RY_ERR_ARG;
+    const size_t nn = ap_rows(n);
+    *bytes = head + ry_align256((size_t)3 * nc * 8) + ry_align256(nn * 8) + 3 * ry_align256(nn * niou * 8);
     return RY_OK;
 }
 
@@ -316,22 +359,17 @@ extern "C" int ryolo_ap_per_class(const unsigned char* tp, const float* conf, co
     if (!ap || !prec_at || !rec_at || !n_labels || !n_pred || !recall_grid || !conf_grid || nconf < 1 || nl < 0) return RY_ERR_ARG;
     if (n > 0 && (!tp || !conf || !pred_cls)) return RY_ERR_ARG;
     if (nl > 0 && !target_cls) return RY_ERR_ARG;
-    size_t sort = 0;
-    if (n > 0) ryolo_sort_workspace_bytes(1, n, &sort);
-    const size_t nn = (size_t)(n > 0 ? n : 1);
+    const size_t nn = ap_rows(n);
     unsigned char* base = reinterpret_cast<unsigned char*>(ws);
-    void* sort_ws = base;                              base += ap_align(sort);
-    int64_t* order = reinterpret_cast<int64_t*>(base); base += ap_align(nn * 8);
-    int64_t* off = reinterpret_cast<int64_t*>(base);   base += ap_align((size_t)3 * nc * 8);
-    double* negc = reinterpret_cast<double*>(base);    base += ap_align(nn * 8);
-    double* rec = reinterpret_cast<double*>(base);     base += ap_align(nn * niou * 8);
-    double* prec = reinterpret_cast<double*>(base);    base += ap_align(nn * niou * 8);
-    double* env = reinterpret_cast<double*>(base);
-    if (n > 0) {
-        const int rc = ryolo_argsort_desc(conf, n, order, sort_ws, sort, stream);       // (confidence desc, index asc): np.argsort(-conf) with ties fixed
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(ap_count_kernel, dim3(1), dim3(AP_THREADS), 0, stream, pred_cls, n, target_cls, nl, nc, n_pred, n_labels, off);
+    int64_t* order = nullptr;
+    const int rc = ap_sorted_order(conf, n, base, order, stream);
+    if (rc) return rc;
+    int64_t* off = ws_take<int64_t>(base, (size_t)3 * nc * 8);
+    double* negc = ws_take<double>(base, nn * 8);
+    double* rec = ws_take<double>(base, nn * niou * 8);
+    double* prec = ws_take<double>(base, nn * niou * 8);
+    double* env = ws_take<double>(base, nn * niou * 8);
+    hipLaunchKernelGGL(class_hist_kernel, dim3(1), dim3(AP_THREADS), 0, stream, pred_cls, n, target_cls, nl, nc, n_pred, n_labels, off);
     hipLaunchKernelGGL(ap_curves_kernel, dim3(nc), dim3(AP_THREADS), 0, stream, tp, conf, pred_cls, order, n, niou, n_pred, n_labels, off, negc, rec, prec);
     hipLaunchKernelGGL(ap_integrate_kernel, dim3(niou, nc), dim3(AP_THREADS), 0, stream, n, niou, n_pred, n_labels, off, rec, prec, env, recall_grid, ap);
     hipLaunchKernelGGL(ap_pr_kernel, dim3(nc), dim3(AP_THREADS), 0, stream, n, n_pred, n_labels, off, negc, rec, prec, conf_grid, nconf, prec_at, rec_at);
@@ -339,158 +377,104 @@ extern "C" int ryolo_ap_per_class(const unsigned char* tp, const float* conf, co
     return RY_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ full-scene matching
-// The same rule as map_match_kernel for ONE scene of thousands of detections and labels, spread over the chip.  The reference never falls
-// back to a second-best label, so the outcome per label does not depend on the walk: the owner of label t is the SMALLEST detection index
-// i (score order) whose best label of its own class is t with IoU > iouv[0], and detection i is a true positive at threshold k iff it
-// owns its best label and that IoU > iouv[k].  One wave per detection finds the best label among the prepared labels of its class and
-// claims it with one atomicMin; a thread per detection then writes its row behind a device-side cursor.  No serial phase, no host read.
-#define SM_WAVES 4
+// ------------------------------------------------------------------------------------------------ full-scene matching: the skeleton
+// ONE scene of thousands of detections and labels, spread over the chip, under either of two protocols.  Neither falls back to a second-best
+// label, so the outcome per label does not depend on a walk: the owner of label t is the SMALLEST detection index i (score order) whose best
+// label of its own class (first maximum) is t with IoU above the threshold, and a detection's row follows from whether it owns its best label.
+// Four launches, no serial phase, no host read: a thread per label prepares it and resets its owner slots; a wave per detection finds the best
+// prepared label of its class and claims it with atomicMin; a thread per detection writes its row behind a device-side cursor; one workgroup
+// moves the cursor.  A rule supplies what differs between the protocols and nothing else: the label row and the prepared label, the prepared
+// detection, the IoU type and function, owner slots per label, the byte of a row at threshold k, whether positives are counted, the nl limit.
+#define MATCH_WAVES 4
 
-static inline size_t sm_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-__device__ __forceinline__ int sm_count(const int32_t* __restrict__ num, int64_t max_det)
+__device__ __forceinline__ int det_count(const int32_t* __restrict__ num, int64_t max_det)
 {
     const int64_t n = *num;
     return (int)(n < 0 ? 0 : (n > max_det ? max_det : n));
 }
 
-__global__ __launch_bounds__(256) void scene_prep_kernel(const float* __restrict__ labels, int64_t nl, BoxPrep* __restrict__ prep,
-                                                         int32_t* __restrict__ owner)
+// the prepared labels [lo, hi) of class `cls`: empty for a NaN, a non-integer or an out-of-range class, and clamped to [0, nl] — a bad
+// table gives wrong numbers, never an access outside prep
+__device__ __forceinline__ void class_range(float cls, const int32_t* __restrict__ cls_off, int nc, int64_t nl, int64_t& lo, int64_t& hi)
 {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= nl) return;
-    const float PI_F = 3.14159274f;
-    const float* tr = labels + t * 6;
-    const float tb[5] = {tr[1], tr[2], tr[3], tr[4], tr[5] / PI_F * 180.f};
-    BoxPrep T;
-    box_prep(tb, T);
-    prep[t] = T;
-    owner[t] = INT_MAX;
-}
-
-__global__ __launch_bounds__(64 * SM_WAVES) void scene_best_kernel(const float* __restrict__ dets, const int32_t* __restrict__ num, int64_t max_det,
-                                                                   const BoxPrep* __restrict__ prep, const int32_t* __restrict__ cls_off, int64_t nl,
-                                                                   int nc, const float* __restrict__ iouv, float* __restrict__ best_iou,
-                                                                   int32_t* __restrict__ best_t, int32_t* __restrict__ owner)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t i = (int64_t)blockIdx.x * SM_WAVES + (threadIdx.x >> 6);
-    if (i >= sm_count(num, max_det)) return;                          // wave-uniform
-    const float* pr = dets + i * 7;
-    const float PI_F = 3.14159274f;
-    const float pb[5] = {pr[0], pr[1], pr[2], pr[3], pr[4] / PI_F * 180.f};   // degrees in registers: dets is never written
-    const float cls = pr[6];
-    int64_t lo = 0, hi = 0;
+    lo = hi = 0;
     if (cls >= 0.f && cls < (float)nc) {                              // NaN fails both
         const int c = (int)cls;
         if ((float)c == cls && c >= 0 && c < nc) {
             lo = cls_off[c];
             hi = cls_off[c + 1];
-            lo = lo < 0 ? 0 : (lo > nl ? nl : lo);                    // a bad table gives wrong numbers, never an access outside prep
+            lo = lo < 0 ? 0 : (lo > nl ? nl : lo);
             hi = hi < lo ? lo : (hi > nl ? nl : hi);
         }
     }
-    float bi = -1.f;
-    int bt = -1;
-    if (lo < hi) {
-        BoxPrep P;
-        box_prep(pb, P);
-        for (int64_t t = lo + lane; t < hi; t += 64) {
-            const BoxPrep T = prep[t];
-            const float v = boxes_far_apart(P, T) ? 0.f : rotated_iou_pair(P, T);
-            if (v > bi) { bi = v; bt = (int)t; }
-        }
-    }
-    // first maximum in label order: larger IoU wins, equal IoU the smaller label index, -1 (no label seen) loses to any index
+}
+
+// n rows fit behind the cursor; when they do not, nothing is written and match_advance_kernel raises the flag
+__device__ __forceinline__ bool rows_fit(int64_t cur, int64_t n, int64_t cap) { return !(cur < 0 || cur > cap || n > cap - cur); }
+
+// first maximum in label order over the wave: larger IoU wins, equal IoU the smaller label index, -1 (no label seen) loses to any index
+template <class F>
+__device__ __forceinline__ void wave_first_max(F& bi, int& bt)
+{
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-        const float oi = __shfl_xor(bi, o, 64);
+        const F oi = __shfl_xor(bi, o, 64);
         const int ot = __shfl_xor(bt, o, 64);
         if (ot >= 0 && (bt < 0 || oi > bi || (oi == bi && ot < bt))) { bi = oi; bt = ot; }
     }
-    if (lane == 0) {
-        best_iou[i] = bi;
-        best_t[i] = bt;
-        if (bt >= 0 && bt < nl && bi > iouv[0]) atomicMin(&owner[bt], (int)i);
+}
+
+// ---- the reference's rule (test.py:130-145; the one map_match_kernel applies per image): labels are rectangles, the IoU is the float pair
+// function shared with NMS, and a detection is a true positive at threshold k iff it owns its best label — claimed at iouv[0], one owner for
+// every threshold — and that IoU > iouv[k].
+struct SceneRule {
+    typedef float Iou;
+    typedef BoxPrep Label;
+    typedef BoxPrep Det;
+    static constexpr int LABEL_FLOATS = 6;                            // cls, x, y, w, h, theta_rad
+    static constexpr bool COUNTS_POSITIVES = false, LABELS_FIRST = true;     // workspace: prep | owner | best_iou | best_t
+    static constexpr int64_t MAX_LABELS = INT_MAX;
+    struct Extra { __host__ __device__ constexpr int slots() const { return 1; } };     // one owner slot per label, nothing else to carry
+    struct Positives {};
+    typedef bool Row;                                                 // the row owns its best label (claimed at iouv[0])
+    static Extra extra(int, const Label*) { return Extra(); }
+
+    static __device__ __forceinline__ void prep_rad(const float* __restrict__ b, BoxPrep& o)
+    {
+        const float PI_F = 3.14159274f;
+        const float d[5] = {b[0], b[1], b[2], b[3], b[4] / PI_F * 180.f};     // degrees in registers: neither labels nor dets are written
+        box_prep(d, o);
     }
-}
+    static __device__ __forceinline__ void prep_label(const float* __restrict__ row, Label& out) { prep_rad(row + 1, out); }
+    static __device__ __forceinline__ void prep_det(const float* __restrict__ pr, Det& D) { prep_rad(pr, D); }
+    static __device__ __forceinline__ Iou iou(const Det& P, const Label& L)
+    {
+        const BoxPrep T = L;
+        return boxes_far_apart(P, T) ? 0.f : rotated_iou_pair(P, T);
+    }
+    static __device__ __forceinline__ Row row(const Extra&, const int32_t* __restrict__ owner, int bt, int i, Iou bi, const float* __restrict__ iouv)
+    {
+        return bi > iouv[0] && owner[bt] == i;
+    }
+    static __device__ __forceinline__ unsigned char status(const Extra&, Row hit, const int32_t* __restrict__, int, int, Iou bi,
+                                                           const float* __restrict__ iouv, int k)
+    {
+        return hit && bi > iouv[k] ? 1 : 0;
+    }
+};
 
-__global__ __launch_bounds__(256) void scene_emit_kernel(const float* __restrict__ dets, const int32_t* __restrict__ num, int64_t max_det, int64_t nl,
-                                                         const float* __restrict__ iouv, int niou, const float* __restrict__ best_iou,
-                                                         const int32_t* __restrict__ best_t, const int32_t* __restrict__ owner,
-                                                         unsigned char* __restrict__ tp, float* __restrict__ conf, float* __restrict__ pcls,
-                                                         int64_t cap, const int64_t* __restrict__ cursor)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t n = sm_count(num, max_det);
-    if (i >= n) return;
-    const int64_t cur = *cursor;
-    if (cur < 0 || cur > cap || n > cap - cur) return;               // overflow: nothing is written (scene_advance_kernel raises the flag)
-    const int bt = best_t[i];
-    const float bi = best_iou[i];
-    const bool hit = bt >= 0 && bt < nl && bi > iouv[0] && owner[bt] == (int)i;
-    unsigned char* row = tp + (cur + i) * niou;
-    for (int k = 0; k < niou; k++) row[k] = hit && bi > iouv[k] ? 1 : 0;
-    conf[cur + i] = dets[i * 7 + 5];
-    pcls[cur + i] = dets[i * 7 + 6];
-}
-
-// stream-ordered after every row is written and every read of the cursor
-__global__ void scene_advance_kernel(const int32_t* __restrict__ num, int64_t max_det, int64_t cap, int64_t* __restrict__ cursor,
-                                     int32_t* __restrict__ overflow)
-{
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    const int64_t n = sm_count(num, max_det), cur = *cursor;
-    if (cur < 0 || cur > cap || n > cap - cur) *overflow = 1;
-    else *cursor = cur + n;
-}
-
-extern "C" int ryolo_scene_match_workspace_bytes(int64_t max_det, int64_t nl, size_t* bytes)
-{
-    if (!bytes || max_det < 0 || nl < 0) return RY_ERR_ARG;
-    *bytes = sm_align((size_t)nl * sizeof(BoxPrep)) + sm_align((size_t)nl * 4) + sm_align((size_t)max_det * 4) + sm_align((size_t)max_det * 4) + 256;
-    return RY_OK;
-}
-
-extern "C" int ryolo_scene_match(const float* dets, const int32_t* num, int64_t max_det, const float* labels, const int32_t* cls_off, int64_t nl,
-                                 int nc, const float* iouv, int niou, unsigned char* tp, float* conf, float* pcls, int64_t cap, int64_t* cursor,
-                                 int32_t* overflow, void* ws, size_t ws_bytes, hipStream_t stream)
-{
-    if (max_det < 0 || nl < 0 || nc < 1 || niou < 1 || cap < 0) return RY_ERR_ARG;
-    if (nc > MAP_MAX_CLASSES || niou > AP_MAX_T || max_det >= INT_MAX || nl >= INT_MAX) return RY_ERR_UNSUPPORTED;
-    if (max_det == 0) return RY_OK;
-    if (!dets || !num || !cls_off || !iouv || !tp || !conf || !pcls || !cursor || !overflow || !ws || (nl > 0 && !labels)) return RY_ERR_ARG;
-    size_t need = 0;
-    ryolo_scene_match_workspace_bytes(max_det, nl, &need);
-    if (ws_bytes < need) return RY_ERR_WORKSPACE;
-    unsigned char* base = reinterpret_cast<unsigned char*>(ws);
-    BoxPrep* prep = reinterpret_cast<BoxPrep*>(base);       base += sm_align((size_t)nl * sizeof(BoxPrep));
-    int32_t* owner = reinterpret_cast<int32_t*>(base);      base += sm_align((size_t)nl * 4);
-    float* best_iou = reinterpret_cast<float*>(base);       base += sm_align((size_t)max_det * 4);
-    int32_t* best_t = reinterpret_cast<int32_t*>(base);
-    if (nl > 0)
-        hipLaunchKernelGGL(scene_prep_kernel, dim3((unsigned)ry_cdiv(nl, 256)), dim3(256), 0, stream, labels, nl, prep, owner);
-    hipLaunchKernelGGL(scene_best_kernel, dim3((unsigned)ry_cdiv(max_det, SM_WAVES)), dim3(64 * SM_WAVES), 0, stream, dets, num, max_det, prep, cls_off,
-                       nl, nc, iouv, best_iou, best_t, owner);
-    hipLaunchKernelGGL(scene_emit_kernel, dim3((unsigned)ry_cdiv(max_det, 256)), dim3(256), 0, stream, dets, num, max_det, nl, iouv, niou, best_iou,
-                       best_t, owner, tp, conf, pcls, cap, cursor);
-    hipLaunchKernelGGL(scene_advance_kernel, dim3(1), dim3(64), 0, stream, num, max_det, cap, cursor, overflow);
-    RY_CHECK_LAUNCH();
-    return RY_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ DOTA-protocol matching
-// The dataset's own rule (include/ryolo.h: ryolo_dota_match) in ryolo_scene_match's launch shape.  What differs: the labels are the
-// annotated quadrilaterals, the IoU is a float64 Sutherland-Hodgman clip of the detection's rectangle against the label's quad, every
-// threshold has its own owner table, and a detection whose best label is "difficult" is ignored (status 2) instead of counted.
+// ---- the DOTA / VOC rule (include/ryolo.h: ryolo_dota_match): the labels are the annotated quadrilaterals, the IoU is a float64
+// Sutherland-Hodgman clip of the detection's rectangle against the label's quad, every threshold has its own owner slot, and a detection
+// whose best label is "difficult" is ignored (status 2) instead of counted.
 // The clip never holds more than 8 vertices (a convex quad cut by four half-planes); it lives in fixed-size arrays, every loop is
 // unrolled and an append is a chain of selects, so nothing is indexed by a run-time value.
-#define DM_WAVES 4
-#define DM_PREP 14      // doubles per prepared label: 4 vertices (x, y) counter-clockwise, area, min x, max x, min y, max y, difficult
 #define DM_LABEL 15     // floats per label row: cls, difficult, quad[8], rect[5]
 
-static inline size_t dm_align(size_t x) { return (x + 255) & ~(size_t)255; }
+struct QuadPrep {       // 14 doubles per prepared label
+    double v[8];        // 4 vertices (x, y), counter-clockwise
+    double area, x0, x1, y0, y1;
+    double hard;        // difficult: 1.0 or 0.0
+};
 
 // corners of (x, y, w, h, theta_rad) in float64: h runs along x before the rotation (lib/general.py: xywha2xyxyxyxy)
 __device__ __forceinline__ void dm_rect_corners(const float* __restrict__ b, double (&vx)[4], double (&vy)[4])
@@ -522,53 +506,6 @@ __device__ __forceinline__ bool dm_finite4(const double (&vx)[4], const double (
 #pragma unroll
     for (int k = 0; k < 4; k++) ok = ok && isfinite(vx[k]) && isfinite(vy[k]);
     return ok;
-}
-
-__global__ __launch_bounds__(256) void dota_prep_kernel(const float* __restrict__ labels, int64_t nl, int niou, double* __restrict__ prep,
-                                                        int32_t* __restrict__ owner)
-{
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= nl) return;
-    const float* r = labels + t * DM_LABEL;
-    double vx[4], vy[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) { vx[k] = (double)r[2 + 2 * k]; vy[k] = (double)r[3 + 2 * k]; }
-    bool quad = dm_finite4(vx, vy);
-    if (quad) {                                                       // strictly convex: the four turns all of one non-zero sign
-        bool pos = true, neg = true;
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const int f = (e + 1) & 3, g = (e + 2) & 3;
-            const double cr = (vx[f] - vx[e]) * (vy[g] - vy[f]) - (vy[f] - vy[e]) * (vx[g] - vx[f]);
-            pos = pos && cr > 0.0;
-            neg = neg && cr < 0.0;
-        }
-        quad = pos || neg;
-    }
-    if (!quad) dm_rect_corners(r + 10, vx, vy);
-    const bool live = dm_finite4(vx, vy);
-    const double s = dm_fan<4>(vx, vy, 4);
-    if (s < 0.0) {                                                    // clockwise in these axes: walk it the other way round
-        double u = vx[1]; vx[1] = vx[3]; vx[3] = u;
-        u = vy[1]; vy[1] = vy[3]; vy[3] = u;
-    }
-    double* p = prep + t * DM_PREP;
-    double x0 = vx[0], x1 = vx[0], y0 = vy[0], y1 = vy[0];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        p[2 * k] = vx[k];
-        p[2 * k + 1] = vy[k];
-        x0 = vx[k] < x0 ? vx[k] : x0; x1 = vx[k] > x1 ? vx[k] : x1;
-        y0 = vy[k] < y0 ? vy[k] : y0; y1 = vy[k] > y1 ? vy[k] : y1;
-    }
-    const double inf = __builtin_huge_val();
-    p[8] = 0.5 * fabs(s);
-    p[9] = live ? x0 : inf;                                           // a label without finite vertices has empty bounds: IoU 0 with everything
-    p[10] = live ? x1 : -inf;
-    p[11] = live ? y0 : inf;
-    p[12] = live ? y1 : -inf;
-    p[13] = r[1] != 0.f ? 1.0 : 0.0;                                  // NaN counts as difficult
-    for (int k = 0; k < niou; k++) owner[t * niou + k] = INT_MAX;
 }
 
 #define DM_APPEND(X, Y)                                           \
@@ -622,120 +559,259 @@ __device__ __forceinline__ double dm_clip_area(const double (&dx)[4], const doub
     return 0.5 * fabs(dm_fan<8>(px, py, n));
 }
 
-__global__ __launch_bounds__(64 * DM_WAVES) void dota_best_kernel(const float* __restrict__ dets, const int32_t* __restrict__ num, int64_t max_det,
-                                                                  const double* __restrict__ prep, const int32_t* __restrict__ cls_off, int64_t nl,
-                                                                  int nc, const float* __restrict__ iouv, int niou, double* __restrict__ best_iou,
-                                                                  int32_t* __restrict__ best_t, int32_t* __restrict__ owner)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t i = (int64_t)blockIdx.x * DM_WAVES + (threadIdx.x >> 6);
-    if (i >= sm_count(num, max_det)) return;                          // wave-uniform
-    const float* pr = dets + i * 7;
-    const float cls = pr[6];
-    int64_t lo = 0, hi = 0;
-    if (cls >= 0.f && cls < (float)nc) {                              // NaN fails both
-        const int c = (int)cls;
-        if ((float)c == cls && c >= 0 && c < nc) {
-            lo = cls_off[c];
-            hi = cls_off[c + 1];
-            lo = lo < 0 ? 0 : (lo > nl ? nl : lo);                    // a bad table gives wrong numbers, never an access outside prep
-            hi = hi < lo ? lo : (hi > nl ? nl : hi);
+struct DotaRule {
+    typedef double Iou;
+    typedef QuadPrep Label;
+    struct Det {
+        double dx[4], dy[4], x0, x1, y0, y1, area;                    // corners, bounds, area
+        bool live;                                                    // every corner finite
+    };
+    static constexpr int LABEL_FLOATS = DM_LABEL;
+    static constexpr bool COUNTS_POSITIVES = true, LABELS_FIRST = false;     // workspace: best_iou | best_t | prep | owner (ryolo.h)
+    static constexpr int64_t MAX_LABELS = INT_MAX / AP_MAX_T;         // owner [nl][niou] is addressed in int32 steps of niou
+    struct Extra { int niou; const Label* prep; __host__ __device__ int slots() const { return niou; } };     // a slot per threshold; the flags
+    struct Positives { const Label* prep; const int32_t* cls_off; int64_t nl; int nc; int64_t* npos; };      // what npos is counted from
+    typedef bool Row;                                                 // the row's best label is difficult
+    static Extra extra(int niou, const Label* prep) { return Extra{niou, prep}; }
+
+    static __device__ __forceinline__ void prep_label(const float* __restrict__ r, Label& p)
+    {
+        double vx[4], vy[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) { vx[k] = (double)r[2 + 2 * k]; vy[k] = (double)r[3 + 2 * k]; }
+        bool quad = dm_finite4(vx, vy);
+        if (quad) {                                                   // strictly convex: the four turns all of one non-zero sign
+            bool pos = true, neg = true;
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int f = (e + 1) & 3, g = (e + 2) & 3;
+                const double cr = (vx[f] - vx[e]) * (vy[g] - vy[f]) - (vy[f] - vy[e]) * (vx[g] - vx[f]);
+                pos = pos && cr > 0.0;
+                neg = neg && cr < 0.0;
+            }
+            quad = pos || neg;
         }
+        if (!quad) dm_rect_corners(r + 10, vx, vy);
+        const bool live = dm_finite4(vx, vy);
+        const double s = dm_fan<4>(vx, vy, 4);
+        if (s < 0.0) {                                                // clockwise in these axes: walk it the other way round
+            double u = vx[1]; vx[1] = vx[3]; vx[3] = u;
+            u = vy[1]; vy[1] = vy[3]; vy[3] = u;
+        }
+        double x0 = vx[0], x1 = vx[0], y0 = vy[0], y1 = vy[0];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            p.v[2 * k] = vx[k];
+            p.v[2 * k + 1] = vy[k];
+            x0 = vx[k] < x0 ? vx[k] : x0; x1 = vx[k] > x1 ? vx[k] : x1;
+            y0 = vy[k] < y0 ? vy[k] : y0; y1 = vy[k] > y1 ? vy[k] : y1;
+        }
+        const double inf = __builtin_huge_val();
+        p.area = 0.5 * fabs(s);
+        p.x0 = live ? x0 : inf;                                      // a label without finite vertices has empty bounds: IoU 0 with everything
+        p.x1 = live ? x1 : -inf;
+        p.y0 = live ? y0 : inf;
+        p.y1 = live ? y1 : -inf;
+        p.hard = r[1] != 0.f ? 1.0 : 0.0;                            // NaN counts as difficult
     }
-    double bi = -1.0;
-    int bt = -1;
-    if (lo < hi) {
-        double dx[4], dy[4];
-        dm_rect_corners(pr, dx, dy);
-        const bool live = dm_finite4(dx, dy);
-        double x0 = dx[0], x1 = dx[0], y0 = dy[0], y1 = dy[0];
+    static __device__ __forceinline__ void prep_det(const float* __restrict__ pr, Det& D)
+    {
+        dm_rect_corners(pr, D.dx, D.dy);
+        D.live = dm_finite4(D.dx, D.dy);
+        D.x0 = D.x1 = D.dx[0];
+        D.y0 = D.y1 = D.dy[0];
 #pragma unroll
         for (int k = 1; k < 4; k++) {
-            x0 = dx[k] < x0 ? dx[k] : x0; x1 = dx[k] > x1 ? dx[k] : x1;
-            y0 = dy[k] < y0 ? dy[k] : y0; y1 = dy[k] > y1 ? dy[k] : y1;
+            D.x0 = D.dx[k] < D.x0 ? D.dx[k] : D.x0; D.x1 = D.dx[k] > D.x1 ? D.dx[k] : D.x1;
+            D.y0 = D.dy[k] < D.y0 ? D.dy[k] : D.y0; D.y1 = D.dy[k] > D.y1 ? D.dy[k] : D.y1;
         }
-        const double ad = 0.5 * fabs(dm_fan<4>(dx, dy, 4));
+        D.area = 0.5 * fabs(dm_fan<4>(D.dx, D.dy, 4));
+    }
+    static __device__ __forceinline__ Iou iou(const Det& D, const Label& L)
+    {
+        double v = 0.0;
+        if (D.live && !(D.x1 < L.x0 || L.x1 < D.x0 || D.y1 < L.y0 || L.y1 < D.y0)) {     // disjoint bounds: IoU 0, exactly
+            const double inter = dm_clip_area(D.dx, D.dy, L.v);
+            const double den = D.area + L.area - inter;
+            v = den <= 0.0 ? 0.0 : inter / den;
+        }
+        return v;
+    }
+    static __device__ __forceinline__ Row row(const Extra& x, const int32_t* __restrict__, int bt, int, Iou, const float* __restrict__)
+    {
+        return x.prep[bt].hard != 0.0;
+    }
+    static __device__ __forceinline__ unsigned char status(const Extra& x, Row hard, const int32_t* __restrict__ owner, int bt, int i, Iou bi,
+                                                           const float* __restrict__ iouv, int k)
+    {
+        return bi > (double)iouv[k] ? (hard ? 2 : (owner[(int64_t)bt * x.niou + k] == i ? 1 : 0)) : 0;
+    }
+};
+
+// ---- the four kernels
+template <class R>
+__global__ __launch_bounds__(256) void match_prep_kernel(const float* __restrict__ labels, int64_t nl, const typename R::Extra x,
+                                                         typename R::Label* __restrict__ prep, int32_t* __restrict__ owner)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nl) return;
+    R::prep_label(labels + t * R::LABEL_FLOATS, prep[t]);
+    const int S = x.slots();
+    for (int k = 0; k < S; k++) owner[t * S + k] = INT_MAX;
+}
+
+template <class R>
+__global__ __launch_bounds__(64 * MATCH_WAVES) void match_best_kernel(const float* __restrict__ dets, const int32_t* __restrict__ num, int64_t max_det,
+                                                                      const typename R::Label* __restrict__ prep,
+                                                                      const int32_t* __restrict__ cls_off, int64_t nl, int nc,
+                                                                      const float* __restrict__ iouv, const typename R::Extra x,
+                                                                      typename R::Iou* __restrict__ best_iou, int32_t* __restrict__ best_t,
+                                                                      int32_t* __restrict__ owner)
+{
+    typedef typename R::Iou Iou;
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * MATCH_WAVES + (threadIdx.x >> 6);
+    if (i >= det_count(num, max_det)) return;                         // wave-uniform
+    const float* pr = dets + i * 7;
+    const float box[5] = {pr[0], pr[1], pr[2], pr[3], pr[4]};         // fetched with the class, not after the class table has answered
+    int64_t lo, hi;
+    class_range(pr[6], cls_off, nc, nl, lo, hi);
+    Iou bi = -1;
+    int bt = -1;
+    if (lo < hi) {
+        typename R::Det D;
+        R::prep_det(box, D);
         for (int64_t t = lo + lane; t < hi; t += 64) {
-            const double* L = prep + t * DM_PREP;
-            double v = 0.0;
-            if (live && !(x1 < L[9] || L[10] < x0 || y1 < L[11] || L[12] < y0)) {     // disjoint bounds: IoU 0, exactly
-                const double inter = dm_clip_area(dx, dy, L);
-                const double den = ad + L[8] - inter;
-                v = den <= 0.0 ? 0.0 : inter / den;
-            }
+            const Iou v = R::iou(D, prep[t]);
             if (v > bi) { bi = v; bt = (int)t; }
         }
     }
-    // first maximum in label order: larger IoU wins, equal IoU the smaller label index, -1 (no label seen) loses to any index
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double oi = __shfl_xor(bi, o, 64);
-        const int ot = __shfl_xor(bt, o, 64);
-        if (ot >= 0 && (bt < 0 || oi > bi || (oi == bi && ot < bt))) { bi = oi; bt = ot; }
-    }
+    wave_first_max(bi, bt);
     if (lane == 0) {
         best_iou[i] = bi;
         best_t[i] = bt;
-        if (bt >= 0 && bt < nl)
-            for (int k = 0; k < niou; k++)
-                if (bi > (double)iouv[k]) atomicMin(&owner[(int64_t)bt * niou + k], (int)i);
+        if (bt >= 0 && bt < nl) {
+            const int S = x.slots();
+            for (int k = 0; k < S; k++)
+                if (bi > (Iou)iouv[k]) atomicMin(&owner[(int64_t)bt * S + k], (int)i);
+        }
     }
 }
 
-__global__ __launch_bounds__(256) void dota_emit_kernel(const float* __restrict__ dets, const int32_t* __restrict__ num, int64_t max_det, int64_t nl,
-                                                        const float* __restrict__ iouv, int niou, const double* __restrict__ best_iou,
-                                                        const int32_t* __restrict__ best_t, const int32_t* __restrict__ owner,
-                                                        const double* __restrict__ prep, unsigned char* __restrict__ status,
-                                                        float* __restrict__ conf, float* __restrict__ pcls, int64_t cap,
-                                                        const int64_t* __restrict__ cursor)
+template <class R>
+__global__ __launch_bounds__(256) void match_emit_kernel(const float* __restrict__ dets, const int32_t* __restrict__ num, int64_t max_det, int64_t nl,
+                                                         const float* __restrict__ iouv, int niou, const typename R::Iou* __restrict__ best_iou,
+                                                         const int32_t* __restrict__ best_t, const int32_t* __restrict__ owner,
+                                                         const typename R::Extra x, unsigned char* __restrict__ rows,
+                                                         float* __restrict__ conf, float* __restrict__ pcls, int64_t cap,
+                                                         const int64_t* __restrict__ cursor)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t n = sm_count(num, max_det);
+    const int64_t n = det_count(num, max_det);
     if (i >= n) return;
     const int64_t cur = *cursor;
-    if (cur < 0 || cur > cap || n > cap - cur) return;               // overflow: nothing is written (dota_advance_kernel raises the flag)
+    if (!rows_fit(cur, n, cap)) return;
     const int bt = best_t[i];
-    const double bi = best_iou[i];
+    const typename R::Iou bi = best_iou[i];
     const bool has = bt >= 0 && bt < nl;
-    const bool hard = has && prep[(int64_t)bt * DM_PREP + 13] != 0.0;
-    unsigned char* row = status + (cur + i) * niou;
-    for (int k = 0; k < niou; k++) {
-        unsigned char s = 0;
-        if (has && bi > (double)iouv[k]) s = hard ? 2 : (owner[(int64_t)bt * niou + k] == (int)i ? 1 : 0);
-        row[k] = s;
-    }
+    const typename R::Row r = has ? R::row(x, owner, bt, (int)i, bi, iouv) : typename R::Row();
+    unsigned char* row = rows + (cur + i) * niou;
+    for (int k = 0; k < niou; k++) row[k] = has ? R::status(x, r, owner, bt, (int)i, bi, iouv, k) : 0;
     conf[cur + i] = dets[i * 7 + 5];
     pcls[cur + i] = dets[i * 7 + 6];
 }
 
-// stream-ordered after every row is written and every read of the cursor: the cursor, the flag, and the positives of the scene's classes
-__global__ __launch_bounds__(256) void dota_advance_kernel(const int32_t* __restrict__ num, int64_t max_det, int64_t cap, int64_t* __restrict__ cursor,
-                                                           int32_t* __restrict__ overflow, const double* __restrict__ prep,
-                                                           const int32_t* __restrict__ cls_off, int64_t nl, int nc, int64_t* __restrict__ npos)
+// stream-ordered after every row is written and every read of the cursor: the cursor, the flag and, under a rule that counts them, the
+// positives of the scene's classes (labels that are not difficult)
+template <class R>
+__global__ __launch_bounds__(64) void match_advance_kernel(const int32_t* __restrict__ num, int64_t max_det, int64_t cap, int64_t* __restrict__ cursor,
+                                                           int32_t* __restrict__ overflow, const typename R::Positives p)
 {
     if (blockIdx.x != 0) return;
-    const int64_t n = sm_count(num, max_det), cur = *cursor;
-    const bool fits = !(cur < 0 || cur > cap || n > cap - cur);
-    __syncthreads();                                                  // every thread has read the cursor before thread 0 moves it
-    if (fits)
-        for (int c = threadIdx.x; c < nc; c += 256) {
-            int64_t lo = cls_off[c], hi = cls_off[c + 1];
-            lo = lo < 0 ? 0 : (lo > nl ? nl : lo);
-            hi = hi < lo ? lo : (hi > nl ? nl : hi);
-            int64_t easy = 0;
-            for (int64_t t = lo; t < hi; t++) easy += prep[t * DM_PREP + 13] == 0.0 ? 1 : 0;
-            npos[c] += easy;
-        }
+    const int64_t n = det_count(num, max_det), cur = *cursor;
+    const bool fits = rows_fit(cur, n, cap);
+    if constexpr (R::COUNTS_POSITIVES) {
+        __syncthreads();                                              // every thread has read the cursor before thread 0 moves it
+        if (fits)
+            for (int c = threadIdx.x; c < p.nc; c += 64) {
+                int64_t lo, hi;
+                class_range((float)c, p.cls_off, p.nc, p.nl, lo, hi);
+                int64_t easy = 0;
+                for (int64_t t = lo; t < hi; t++) easy += p.prep[t].hard == 0.0 ? 1 : 0;
+                p.npos[c] += easy;
+            }
+    }
     if (threadIdx.x == 0) {
         if (fits) *cursor = cur + n;
         else *overflow = 1;
     }
 }
 
+// ---- the host side: the workspace holds  best_iou [max_det] Iou | best_t [max_det]  and  prep [nl] Label | owner [nl][slots],  in the
+// rule's order
+template <class R>
+static size_t match_workspace_bytes(int64_t max_det, int64_t nl, int niou)
+{
+    return ry_align256((size_t)max_det * sizeof(typename R::Iou)) + ry_align256((size_t)max_det * 4) +
+           ry_align256((size_t)nl * sizeof(typename R::Label)) + ry_align256((size_t)nl * R::extra(niou, nullptr).slots() * 4) + 256;
+}
+
+template <class R>
+static int match_launch(const float* dets, const int32_t* num, int64_t max_det, const float* labels, const int32_t* cls_off, int64_t nl, int nc,
+                        const float* iouv, int niou, unsigned char* rows, float* conf, float* pcls, int64_t cap, int64_t* cursor,
+                        int32_t* overflow, int64_t* npos, void* ws, size_t ws_bytes, hipStream_t stream)
+{
+    typedef typename R::Iou Iou;
+    typedef typename R::Label Label;
+    if (max_det < 0 || nl < 0 || nc < 1 || niou < 1 || cap < 0) return RY_ERR_ARG;
+    if (nc > MAP_MAX_CLASSES || niou > AP_MAX_T || max_det >= INT_MAX || nl >= R::MAX_LABELS) return RY_ERR_UNSUPPORTED;
+    if (max_det == 0 && !R::COUNTS_POSITIVES) return RY_OK;           // no row to write and nothing to count: before any pointer is looked at
+    if (!cls_off || !cursor || !overflow || !num || !ws || (nl > 0 && !labels) || (R::COUNTS_POSITIVES && !npos)) return RY_ERR_ARG;
+    if (max_det > 0 && (!dets || !iouv || !rows || !conf || !pcls)) return RY_ERR_ARG;
+    if (ws_bytes < match_workspace_bytes<R>(max_det, nl, niou)) return RY_ERR_WORKSPACE;
+    unsigned char* base = reinterpret_cast<unsigned char*>(ws);
+    const size_t owner_bytes = (size_t)nl * R::extra(niou, nullptr).slots() * 4;
+    Label* prep = nullptr;
+    int32_t* owner = nullptr;
+    if (R::LABELS_FIRST) { prep = ws_take<Label>(base, (size_t)nl * sizeof(Label)); owner = ws_take<int32_t>(base, owner_bytes); }
+    Iou* best_iou = ws_take<Iou>(base, (size_t)max_det * sizeof(Iou));
+    int32_t* best_t = ws_take<int32_t>(base, (size_t)max_det * 4);
+    if (!R::LABELS_FIRST) { prep = ws_take<Label>(base, (size_t)nl * sizeof(Label)); owner = ws_take<int32_t>(base, owner_bytes); }
+    const typename R::Extra x = R::extra(niou, prep);
+    if (nl > 0)
+        hipLaunchKernelGGL(match_prep_kernel<R>, dim3((unsigned)ry_cdiv(nl, 256)), dim3(256), 0, stream, labels, nl, x, prep, owner);
+    if (max_det > 0) {
+        hipLaunchKernelGGL(match_best_kernel<R>, dim3((unsigned)ry_cdiv(max_det, MATCH_WAVES)), dim3(64 * MATCH_WAVES), 0, stream, dets, num, max_det,
+                           prep, cls_off, nl, nc, iouv, x, best_iou, best_t, owner);
+        hipLaunchKernelGGL(match_emit_kernel<R>, dim3((unsigned)ry_cdiv(max_det, 256)), dim3(256), 0, stream, dets, num, max_det, nl, iouv, niou,
+                           best_iou, best_t, owner, x, rows, conf, pcls, cap, cursor);
+    }
+    typename R::Positives pos{};
+    if constexpr (R::COUNTS_POSITIVES) pos = typename R::Positives{prep, cls_off, nl, nc, npos};
+    hipLaunchKernelGGL(match_advance_kernel<R>, dim3(1), dim3(64), 0, stream, num, max_det, cap, cursor, overflow, pos);
+    RY_CHECK_LAUNCH();
+    return RY_OK;
+}
+
+extern "C" int ryolo_scene_match_workspace_bytes(int64_t max_det, int64_t nl, size_t* bytes)
+{
+    if (!bytes || max_det < 0 || nl < 0) return RY_ERR_ARG;
+    *bytes = match_workspace_bytes<SceneRule>(max_det, nl, 1);
+    return RY_OK;
+}
+
+extern "C" int ryolo_scene_match(const float* dets, const int32_t* num, int64_t max_det, const float* labels, const int32_t* cls_off, int64_t nl,
+                                 int nc, const float* iouv, int niou, unsigned char* tp, float* conf, float* pcls, int64_t cap, int64_t* cursor,
+                                 int32_t* overflow, void* ws, size_t ws_bytes, hipStream_t stream)
+{
+    return match_launch<SceneRule>(dets, num, max_det, labels, cls_off, nl, nc, iouv, niou, tp, conf, pcls, cap, cursor, overflow, nullptr, ws,
+                                   ws_bytes, stream);
+}
+
 extern "C" int ryolo_dota_match_workspace_bytes(int64_t max_det, int64_t nl, int niou, size_t* bytes)
 {
     if (!bytes || max_det < 0 || nl < 0 || niou < 1 || niou > AP_MAX_T) return RY_ERR_ARG;
-    *bytes = dm_align((size_t)max_det * 8) + dm_align((size_t)max_det * 4) + dm_align((size_t)nl * DM_PREP * 8) + dm_align((size_t)nl * niou * 4) + 256;
+    *bytes = match_workspace_bytes<DotaRule>(max_det, nl, niou);
     return RY_OK;
 }
 
@@ -743,52 +819,13 @@ extern "C" int ryolo_dota_match(const float* dets, const int32_t* num, int64_t m
                                 int nc, const float* iouv, int niou, unsigned char* status, float* conf, float* pcls, int64_t cap, int64_t* cursor,
                                 int32_t* overflow, int64_t* npos, void* ws, size_t ws_bytes, hipStream_t stream)
 {
-    if (max_det < 0 || nl < 0 || nc < 1 || niou < 1 || cap < 0) return RY_ERR_ARG;
-    if (nc > MAP_MAX_CLASSES || niou > AP_MAX_T || max_det >= INT_MAX || nl >= INT_MAX / AP_MAX_T) return RY_ERR_UNSUPPORTED;
-    if (!cls_off || !cursor || !overflow || !npos || !num || !ws || (nl > 0 && !labels)) return RY_ERR_ARG;
-    if (max_det > 0 && (!dets || !iouv || !status || !conf || !pcls)) return RY_ERR_ARG;
-    size_t need = 0;
-    ryolo_dota_match_workspace_bytes(max_det, nl, niou, &need);
-    if (ws_bytes < need) return RY_ERR_WORKSPACE;
-    unsigned char* base = reinterpret_cast<unsigned char*>(ws);
-    double* best_iou = reinterpret_cast<double*>(base);     base += dm_align((size_t)max_det * 8);
-    int32_t* best_t = reinterpret_cast<int32_t*>(base);     base += dm_align((size_t)max_det * 4);
-    double* prep = reinterpret_cast<double*>(base);         base += dm_align((size_t)nl * DM_PREP * 8);
-    int32_t* owner = reinterpret_cast<int32_t*>(base);
-    if (nl > 0)
-        hipLaunchKernelGGL(dota_prep_kernel, dim3((unsigned)ry_cdiv(nl, 256)), dim3(256), 0, stream, labels, nl, niou, prep, owner);
-    if (max_det > 0) {
-        hipLaunchKernelGGL(dota_best_kernel, dim3((unsigned)ry_cdiv(max_det, DM_WAVES)), dim3(64 * DM_WAVES), 0, stream, dets, num, max_det, prep,
-                           cls_off, nl, nc, iouv, niou, best_iou, best_t, owner);
-        hipLaunchKernelGGL(dota_emit_kernel, dim3((unsigned)ry_cdiv(max_det, 256)), dim3(256), 0, stream, dets, num, max_det, nl, iouv, niou, best_iou,
-                           best_t, owner, prep, status, conf, pcls, cap, cursor);
-    }
-    hipLaunchKernelGGL(dota_advance_kernel, dim3(1), dim3(256), 0, stream, num, max_det, cap, cursor, overflow, prep, cls_off, nl, nc, npos);
-    RY_CHECK_LAUNCH();
-    return RY_OK;
+    return match_launch<DotaRule>(dets, num, max_det, labels, cls_off, nl, nc, iouv, niou, status, conf, pcls, cap, cursor, overflow, npos, ws,
+                                  ws_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ VOC AP from the DOTA statistics
 // Per class and threshold: the rows of the class in confidence order (the sort of ryolo_ap_per_class), rows with status 2 left out, running
 // true / false positive counts by the ballot / popcount scans of ap_curves_kernel, then the 11-point VOC07 mean or the VOC12 area.
-__global__ __launch_bounds__(AP_THREADS) void voc_count_kernel(const float* __restrict__ pcls, int64_t n, int nc, int64_t* __restrict__ cnt,
-                                                               int64_t* __restrict__ off)
-{
-    __shared__ int c_p[MAP_MAX_CLASSES];
-    const int tid = threadIdx.x;
-    for (int k = tid; k < nc; k += AP_THREADS) c_p[k] = 0;
-    __syncthreads();
-    for (int64_t i = tid; i < n; i += AP_THREADS) {
-        const float c = pcls[i];
-        const int k = (int)c;
-        if (k >= 0 && k < nc && (float)k == c) atomicAdd(&c_p[k], 1);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int64_t run = 0;
-        for (int k = 0; k < nc; k++) { cnt[k] = c_p[k]; off[k] = run; run += c_p[k]; }
-    }
-}
 
 // grid (T, classes): recall / precision after every counted row of the class at threshold t, and how many rows were counted
 __global__ __launch_bounds__(AP_THREADS) void voc_curves_kernel(const unsigned char* __restrict__ status, const float* __restrict__ pcls,
@@ -839,7 +876,7 @@ __global__ __launch_bounds__(AP_THREADS) void voc_integrate_kernel(int64_t n, in
                                                                    const double* __restrict__ rec, const double* __restrict__ prec,
                                                                    double* __restrict__ env, const double* __restrict__ grid11, double* __restrict__ ap)
 {
-    __shared__ double wmax[16][11], carry_s, term[AP_THREADS], sum_s;
+    __shared__ double wmax[16][11], term[AP_THREADS], sum_s;
     const int t = blockIdx.x, k = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (npos[k] <= 0) { if (tid == 0) ap[(int64_t)k * T + t] = __builtin_nan(""); return; }
     const int64_t m = used[(int64_t)k * T + t];
@@ -874,31 +911,8 @@ __global__ __launch_bounds__(AP_THREADS) void voc_integrate_kernel(int64_t n, in
         }
         return;
     }
-    if (tid == 0) { carry_s = 0.0; sum_s = 0.0; }                      // mpre ends with 0
-    __syncthreads();
-    for (int64_t hi = m; hi > 0; hi -= AP_THREADS) {                   // running maximum from the right, chunk by chunk
-        const int64_t i = hi - AP_THREADS + tid;
-        double v = i >= 0 ? p_[i] : 0.0;
-        for (int d = 1; d < 64; d <<= 1) {
-            const double o = __shfl_down(v, d, 64);
-            if (lane + d < 64) v = fmax(v, o);
-        }
-        if (lane == 0) wmax[wave][0] = v;
-        __syncthreads();
-        double later = carry_s;
-        for (int w = wave + 1; w < 16; w++) later = fmax(later, wmax[w][0]);
-        v = fmax(v, later);
-        if (i >= 0) e_[i] = v;
-        __syncthreads();
-        if (tid == 0) {
-            double c = carry_s;
-            for (int w = 0; w < 16; w++) c = fmax(c, wmax[w][0]);
-            carry_s = c;
-        }
-        __syncthreads();
-    }
-    __threadfence_block();
-    __syncthreads();
+    if (tid == 0) sum_s = 0.0;
+    suffix_max_envelope(p_, e_, m);                                    // mpre ends with 0
     // sum over j of (mrec[j + 1] - mrec[j]) * mpre[j + 1], ascending, one after the other; a term where mrec does not change is +0 and
     // leaves the sum as it is, and the last one, (1 - rec[m - 1]) * 0, likewise
     for (int64_t j0 = 0; j0 < m; j0 += AP_THREADS) {
@@ -918,11 +932,9 @@ __global__ __launch_bounds__(AP_THREADS) void voc_integrate_kernel(int64_t n, in
 
 extern "C" int ryolo_ap_voc_workspace_bytes(int64_t n, int niou, int nc, size_t* bytes)
 {
-    if (!bytes || n < 0 || niou < 1 || niou > AP_MAX_T || nc < 1 || nc > MAP_MAX_CLASSES) return RY_ERR_ARG;
-    size_t sort = 0;
-    if (n > 0 && ryolo_sort_workspace_bytes(1, n, &sort) != RY_OK) return RY_ERR_ARG;
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    *bytes = ap_align(sort) + ap_align(nn * 8) + ap_align((size_t)nc * 8) + ap_align((size_t)nc * niou * 8) + 3 * ap_align(nn * niou * 8);
+    size_t head = 0;
+    if (!bytes || ap_head_bytes(n, niou, nc, &head) != RY_OK) return RY_ERR_ARG;
+    *bytes = head + ry_align256((size_t)nc * 8) + ry_align256((size_t)nc * niou * 8) + 3 * ry_align256(ap_rows(n) * niou * 8);
     return RY_OK;
 }
 
@@ -935,22 +947,18 @@ extern "C" int ryolo_ap_voc(const unsigned char* status, const float* conf, cons
     if (!ws || ws_bytes < need) return RY_ERR_WORKSPACE;
     if (!ap || !n_pred || !npos || !grid11) return RY_ERR_ARG;
     if (n > 0 && (!status || !conf || !pred_cls)) return RY_ERR_ARG;
-    size_t sort = 0;
-    if (n > 0) ryolo_sort_workspace_bytes(1, n, &sort);
-    const size_t nn = (size_t)(n > 0 ? n : 1);
+    const size_t nn = ap_rows(n);
     unsigned char* base = reinterpret_cast<unsigned char*>(ws);
-    void* sort_ws = base;                              base += ap_align(sort);
-    int64_t* order = reinterpret_cast<int64_t*>(base); base += ap_align(nn * 8);
-    int64_t* off = reinterpret_cast<int64_t*>(base);   base += ap_align((size_t)nc * 8);
-    int64_t* used = reinterpret_cast<int64_t*>(base);  base += ap_align((size_t)nc * niou * 8);
-    double* rec = reinterpret_cast<double*>(base);     base += ap_align(nn * niou * 8);
-    double* prec = reinterpret_cast<double*>(base);    base += ap_align(nn * niou * 8);
-    double* env = reinterpret_cast<double*>(base);
-    if (n > 0) {
-        const int rc = ryolo_argsort_desc(conf, n, order, sort_ws, sort, stream);       // (confidence desc, index asc)
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(voc_count_kernel, dim3(1), dim3(AP_THREADS), 0, stream, pred_cls, n, nc, n_pred, off);
+    int64_t* order = nullptr;
+    const int rc = ap_sorted_order(conf, n, base, order, stream);
+    if (rc) return rc;
+    int64_t* off = ws_take<int64_t>(base, (size_t)nc * 8);
+    int64_t* used = ws_take<int64_t>(base, (size_t)nc * niou * 8);
+    double* rec = ws_take<double>(base, nn * niou * 8);
+    double* prec = ws_take<double>(base, nn * niou * 8);
+    double* env = ws_take<double>(base, nn * niou * 8);
+    hipLaunchKernelGGL(class_hist_kernel, dim3(1), dim3(AP_THREADS), 0, stream, pred_cls, n, (const float*)nullptr, (int64_t)0, nc, n_pred,
+                       (int64_t*)nullptr, off);
     hipLaunchKernelGGL(voc_curves_kernel, dim3(niou, nc), dim3(AP_THREADS), 0, stream, status, pred_cls, order, n, niou, n_pred, npos, off, rec, prec, used);
     hipLaunchKernelGGL(voc_integrate_kernel, dim3(niou, nc), dim3(AP_THREADS), 0, stream, n, niou, metric, npos, off, used, rec, prec, env, grid11, ap);
     RY_CHECK_LAUNCH();

@@ -39,7 +39,6 @@ struct ScaleWs {
     float* gbox;              // [cap][8]: d(loss)/d(x, y, w, h[, a] logits) of the match
     int cap, cells, nblk_match, nblk_obj;
 };
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Layout (r05): [count x 3 | owner x 3, head x 3 | per scale: rec, frec, part_match, part_obj, next, gbox].  Only the first region is cleared (to
 // zero) and the second filled with -1 per call — two fills instead of the seven of r02-r04, which also cleared the whole workspace (190 MB at the
@@ -59,17 +58,17 @@ __host__ __device__ static inline void carve(const LossParams& p, ScaleWs* s, si
         s[i].count = reinterpret_cast<int*>(base + off); off += 256;
     }
     if (ff_off) *ff_off = off;
-    for (int i = 0; i < 3; i++) { s[i].owner = reinterpret_cast<int*>(base + off); off += al256((size_t)s[i].cells * 4); }
-    for (int i = 0; i < 3; i++) { s[i].head = reinterpret_cast<int*>(base + off); off += al256((size_t)s[i].cells * 4); }
+    for (int i = 0; i < 3; i++) { s[i].owner = reinterpret_cast<int*>(base + off); off += ry_align256((size_t)s[i].cells * 4); }
+    for (int i = 0; i < 3; i++) { s[i].head = reinterpret_cast<int*>(base + off); off += ry_align256((size_t)s[i].cells * 4); }
     if (ff_bytes) *ff_bytes = off - 768;
     for (int i = 0; i < 3; i++) {
         const int cap = s[i].cap;
-        s[i].rec = reinterpret_cast<int*>(base + off); off += al256((size_t)cap * 8 * 4);
-        s[i].frec = reinterpret_cast<float*>(base + off); off += al256((size_t)cap * 8 * 4);
-        s[i].part_match = reinterpret_cast<float*>(base + off); off += al256((size_t)(s[i].nblk_match > 0 ? s[i].nblk_match : 1) * 4 * 4);
-        s[i].part_obj = reinterpret_cast<float*>(base + off); off += al256((size_t)s[i].nblk_obj * 4);
-        s[i].next = reinterpret_cast<int*>(base + off); off += al256((size_t)cap * 4);
-        s[i].gbox = reinterpret_cast<float*>(base + off); off += al256((size_t)cap * 8 * 4);
+        s[i].rec = reinterpret_cast<int*>(base + off); off += ry_align256((size_t)cap * 8 * 4);
+        s[i].frec = reinterpret_cast<float*>(base + off); off += ry_align256((size_t)cap * 8 * 4);
+        s[i].part_match = reinterpret_cast<float*>(base + off); off += ry_align256((size_t)(s[i].nblk_match > 0 ? s[i].nblk_match : 1) * 4 * 4);
+        s[i].part_obj = reinterpret_cast<float*>(base + off); off += ry_align256((size_t)s[i].nblk_obj * 4);
+        s[i].next = reinterpret_cast<int*>(base + off); off += ry_align256((size_t)cap * 4);
+        s[i].gbox = reinterpret_cast<float*>(base + off); off += ry_align256((size_t)cap * 8 * 4);
     }
     *total = off;
 }

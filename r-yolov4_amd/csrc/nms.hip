@@ -296,13 +296,11 @@ __global__ void diag_iou_kernel(const float* __restrict__ b1, const float* __res
 }
 
 // -------------------------------------------------------------------------------------------------- C ABI
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 extern "C" int ryolo_nms_workspace_bytes(int batch, int64_t nmax, size_t* bytes)
 {
     if (!bytes || batch < 0 || nmax < 0) return RY_ERR_ARG;
     const int64_t nw = ry_cdiv(nmax, TILE);
-    *bytes = align256((size_t)batch * nmax * sizeof(BoxPrep)) + align256((size_t)batch * nmax * nw * 8) + 256;
+    *bytes = ry_align256((size_t)batch * nmax * sizeof(BoxPrep)) + ry_align256((size_t)batch * nmax * nw * 8) + 256;
     return RY_OK;
 }
 
@@ -321,7 +319,7 @@ extern "C" int ryolo_nms_rotated_batched(const float* boxes, const int32_t* coun
     const int nw = (int)ry_cdiv(nmax, TILE);
     BoxPrep* prep = reinterpret_cast<BoxPrep*>(ws);
     unsigned long long* mask = reinterpret_cast<unsigned long long*>(
-        reinterpret_cast<char*>(ws) + align256((size_t)batch * nmax * sizeof(BoxPrep)));
+        reinterpret_cast<char*>(ws) + ry_align256((size_t)batch * nmax * sizeof(BoxPrep)));
     const int64_t total = (int64_t)batch * nmax;
     hipLaunchKernelGGL(nms_prep_kernel, dim3((unsigned)ry_cdiv(total, 256)), dim3(256), 0, stream, boxes, total, prep);
     const int prune = iou_thr > 1e-6f ? 1 : 0;
@@ -348,7 +346,7 @@ extern "C" int ryolo_nms_owner(const int32_t* counts, int batch, int64_t nmax, c
     if (ws_bytes < need) return RY_ERR_WORKSPACE;
     const int nw = (int)ry_cdiv(nmax, TILE);
     const unsigned long long* mask = reinterpret_cast<const unsigned long long*>(
-        reinterpret_cast<const char*>(ws) + align256((size_t)batch * nmax * sizeof(BoxPrep)));
+        reinterpret_cast<const char*>(ws) + ry_align256((size_t)batch * nmax * sizeof(BoxPrep)));
     hipLaunchKernelGGL(nms_owner_kernel, dim3((unsigned)ry_cdiv(nw, 4), batch), dim3(256), 0, stream, mask, counts, nmax, nw, keep,
                        keep_stride, num_keep, owner);
     RY_CHECK_LAUNCH();
@@ -361,9 +359,9 @@ extern "C" int ryolo_box_iou_rotated(const float* b1, int n, const float* b2, in
     if (n < 0 || m < 0) return RY_ERR_ARG;
     if (n == 0 || m == 0) return RY_OK;
     if (!b1 || !b2 || !out || !ws) return RY_ERR_ARG;
-    if (ws_bytes < align256((size_t)n * sizeof(BoxPrep)) + (size_t)m * sizeof(BoxPrep)) return RY_ERR_WORKSPACE;
+    if (ws_bytes < ry_align256((size_t)n * sizeof(BoxPrep)) + (size_t)m * sizeof(BoxPrep)) return RY_ERR_WORKSPACE;
     BoxPrep* p1 = reinterpret_cast<BoxPrep*>(ws);
-    BoxPrep* p2 = reinterpret_cast<BoxPrep*>(reinterpret_cast<char*>(ws) + align256((size_t)n * sizeof(BoxPrep)));
+    BoxPrep* p2 = reinterpret_cast<BoxPrep*>(reinterpret_cast<char*>(ws) + ry_align256((size_t)n * sizeof(BoxPrep)));
     hipLaunchKernelGGL(nms_prep_kernel, dim3((unsigned)ry_cdiv(n, 256)), dim3(256), 0, stream, b1, (int64_t)n, p1);
     hipLaunchKernelGGL(nms_prep_kernel, dim3((unsigned)ry_cdiv(m, 256)), dim3(256), 0, stream, b2, (int64_t)m, p2);
     hipLaunchKernelGGL(pairwise_iou_kernel, dim3((unsigned)ry_cdiv(m, TILE), (unsigned)ry_cdiv(n, TILE)), dim3(256), 0, stream,

@@ -7,7 +7,8 @@ restatement tests/dota_eval_ref.py.
              non-convex quads, thresholds 0.5 / 0.75 / 0.9); every num around the wave size; no labels; labels as boxes; `out` untouched;
              accumulation; overflow; determinism; a captured graph; status == 1 equal to ryolo_scene_match's tp on the cases "square" and "cross";
   AP         ryolo_ap_voc within 1e-12 for both metrics on the matched scene and on 20 000 random rows x 16 classes with confidence ties;
-  evaluator  DotaEvaluator / evaluate_scenes_dota with a TiledDetector on two random scenes.
+  evaluator  DotaEvaluator / evaluate_scenes_dota with a TiledDetector on two random scenes; DotaEvaluator and SceneEvaluator interleaved on one
+             stream leave each with the bytes it has alone (the two share one matching skeleton and one base class).
 No row and no case is left out of a comparison: tests/test_dota_eval_cpu.py asserts that the generated cases keep their decision gaps (the
 restatement and the kernel differ in cos / sin by an ulp or two), and the gaps are asserted again here with the rectangles the device
 computes for the quads."""
@@ -374,6 +375,33 @@ def test_evaluator_overflow_raises(scene):
     ev.reset()
     ev.add(_padded(sc["dets"]), _num(360), sc["quads"], sc["classes"], sc["difficult"])
     assert np.array_equal(ev.stats()[0], m["status"])
+
+
+def test_interleaved_with_the_scene_evaluator_equals_each_alone(scene):
+    """The two rules run through one skeleton on the host and on the device: scene, dota, scene, dota on one device and stream (n = 65, 65,
+    1, 1: across a workgroup of waves and the 64 lanes, then a single row) must leave each evaluator with exactly the bytes it has after the
+    same two scenes alone — no state of one rule reaches the other.  The alone runs are held to the oracles by the tests above and by
+    tests/test_gpu_scene_eval.py."""
+    from ryolov4_amd.lib.dota_eval import DotaEvaluator
+    from ryolov4_amd.lib.scene_eval import SceneEvaluator
+    from tests import scene_eval_ref as S
+    sc, iouv, _ = scene
+    sdets, sboxes, sclasses = S.case("mixed")
+
+    def run(which):
+        evs = {"scene": SceneEvaluator(NC, capacity=100, device=DEV), "dota": DotaEvaluator(NC, iouv=iouv, capacity=100, device=DEV)}
+        for n in (65, 1):
+            if "scene" in which:
+                evs["scene"].add(_padded(sdets), _num(n), sboxes, sclasses)
+            if "dota" in which:
+                evs["dota"].add(_padded(sc["dets"]), _num(n), sc["quads"], sc["classes"], sc["difficult"])
+        return {k: evs[k].stats() for k in which}
+
+    both, alone = run(("scene", "dota")), {**run(("scene",)), **run(("dota",))}
+    for k in ("scene", "dota"):
+        assert len(both[k]) == len(alone[k]) == 4 and both[k][0].shape[0] == 66 and both[k][0][:, 0].sum() >= 10
+        for a, b in zip(both[k], alone[k]):
+            assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), k
 
 
 # ---------------------------------------------------------------------------------------------- end to end with a detector
