@@ -18,7 +18,9 @@ import torch
 
 from .. import hip
 from . import arena
+from . import params as P
 from . import structs as S
+from .params import _classes_dgrad_s2, _fill_class, _taps_dgrad_s1, _taps_dgrad_s2d, _taps_fwd  # noqa: F401  (the engine's own tap tables)
 
 BF16 = torch.bfloat16
 
@@ -106,40 +108,6 @@ class TRef:
     def to_nchw(self, grad=False):
         t = self.buf.g if grad else self.buf.t
         return t.view(self.N, self.H, self.W, self.ld)[..., self.c0:self.c0 + self.C].permute(0, 3, 1, 2).float().contiguous()
-
-
-def _taps_fwd(k, pad):
-    return [(r - pad, s - pad, r * k + s) for r in range(k) for s in range(k)]
-
-
-def _taps_dgrad_s1(k, pad):
-    """Stride-1 data gradient: a correlation of dY with mirrored taps; weight slot r * k + c of the [Cin][tap][Cout] image."""
-    return [(pad - r, pad - c, r * k + c) for r in range(k) for c in range(k)]
-
-
-def _classes_dgrad_s2(k, pad):
-    """Stride-2 data gradient as four output-parity classes [(taps, ph, pw)]: dx[2a + ph][2b + pw] sums only the taps (r, c) whose
-    input row 2 oh - pad + r can be 2a + ph, i.e. (ph + pad - r) even (1 / 2 / 2 / 4 live taps for k = 3, pad = 1), read at
-    dY[a + (ph + pad - r) / 2][b + (pw + pad - c) / 2]."""
-    classes = []
-    for ph in range(2):
-        for pw in range(2):
-            taps = [((ph + pad - r) // 2, (pw + pad - c) // 2, r * k + c) for r in range(k) for c in range(k)
-                    if (ph + pad - r) % 2 == 0 and (pw + pad - c) % 2 == 0]
-            classes.append((taps, ph, pw))
-    return classes
-
-
-def _taps_dgrad_s2d():
-    """Space-to-depth form of the 3x3 stride-2 pad-1 data gradient (weights from ryolo_pack_s2d): 2 x 2 taps over the dY grid."""
-    return [(da, db, 2 * da + db) for da in range(2) for db in range(2)]
-
-
-def _fill_class(tc, taps, oh_add=0, ow_add=0):
-    tc.ntaps = len(taps)
-    tc.oh_add, tc.ow_add = oh_add, ow_add
-    for i, (dh, dw, wi) in enumerate(taps):
-        tc.dh[i], tc.dw[i], tc.widx[i] = dh, dw, wi
 
 
 class Graph:
@@ -272,9 +240,10 @@ class Graph:
             by = p.NB * p.IH * p.IW * p.Cin * 2 + p.Nout * p.wtaps * p.Cin * 2 + outb
             kern = S.I()
             hip.call("ryolo_conv_gemm_plan", p, S.I(), kern)
-            fam, kv = kern.value & 0xff, kern.value
+            kw = S.KernelWord(kern.value)
+            fam = kw.family
             if fam == 1:
-                return (f"conv3x3_patch_kernel<256x{((kv >> 16) & 15) * 32}>", fl, by)
+                return (f"conv3x3_patch_kernel<256x{kw.tile_cols}>", fl, by)
             if fam == 2:
                 # plain pointwise launches of the persistent kernel (on by size since r04) belong to the K <= 256 / K > 256 split of bench.py
                 # like the generic kernel's 1x1 instantiation; its tapped / pool-gradient instantiations do not
@@ -288,10 +257,10 @@ class Graph:
             if fam == 6:
                 return ("conv3x3s2_c32_dgrad_kernel", fl, by)
             if fam == 4:
-                return (f"gemm256_kernel<256x{((kv >> 16) & 15) * 32}>", fl, by, "K<=256" if p.Cin <= 256 else "K>256")
+                return (f"gemm256_kernel<256x{kw.tile_cols}>", fl, by, "K<=256" if p.Cin <= 256 else "K>256")
             # the generic kernel's instantiations as rocprofv3 lists them: tile shape, and the 1x1 form (no tap table / tile decomposition)
-            kind = f"conv_gemm_kernel<{((kv >> 12) & 15) * 64}x{((kv >> 16) & 15) * 32}{',1x1' if kv & 0x100 else ''}>"
-            if kv & 0x100:
+            kind = f"conv_gemm_kernel<{kw.tile_rows}x{kw.tile_cols}{',1x1' if kw.is_1x1 else ''}>"
+            if kw.is_1x1:
                 # the pointwise class holds two regimes: short-K layers are memory streams, K > 256 layers are MFMA-side;
                 # the fourth field lets bench.py report a roofline for each
                 return (kind, fl, by, "K<=256" if p.Cin <= 256 else "K>256")
@@ -447,50 +416,30 @@ class Graph:
         self.rt.side_event = None
 
     # ------------------------------------------------------------------ convolution
-    def _gemm(self, tape, A, Aptr, W, Nout, wtaps, gemm_cin, OH, OW, stride, classes, epi, out_ptr, ldC, full=None,
-              coeffs=None, act=0, bias=None, s2d=0, pool=None, head=None):
-        """Emit one ryolo_conv_gemm launch.  For epi == EPI_STATS the partial-statistics buffer is sized by the library's plan
-        (one [2][Nout] row per M tile of the kernel it will run) and returned."""
-        p = S.ConvGemmParams()
-        p.A, p.NB, p.IH, p.IW, p.Cin, p.ldA = Aptr, A.N, A.H, A.W, gemm_cin, A.ld
-        p.W, p.Nout, p.wtaps = W.data_ptr(), Nout, wtaps
-        p.OH, p.OW, p.sh, p.sw = OH, OW, stride, stride
-        if full is None:
-            p.oh_mul, p.ow_mul, p.OHf, p.OWf = 1, 1, OH, OW
-        else:
-            p.oh_mul, p.ow_mul, p.OHf, p.OWf = full
-        p.nclasses = len(classes)
-        for i, (taps, oa, wa) in enumerate(classes):
-            _fill_class(p.cls[i], taps, oa, wa)
-        p.epi, p.out, p.ldC = epi, out_ptr, ldC
-        if coeffs is not None:
-            Cn = coeffs.shape[1]
-            p.scale, p.shift = coeffs.data_ptr() + 2 * Cn * 4, coeffs.data_ptr() + 3 * Cn * 4
-        p.act = act
-        p.bias = bias
-        p.zeros = self.rt.zeros.data_ptr()
-        p.a_bytes, p.w_bytes = A.span_bytes, W.numel() * 2
-        p.pipe = self.rt.gemm_pipe
-        p.s2d_cin = s2d
-        if head is not None:                            # (attrs, och, ImplicitM pointer or None, compact objectness pointer or None)
-            p.head_attrs, p.head_och, p.scale, p.stats = head
-        if pool is not None:
-            p.pool_idx, p.pool_dz, p.pool_ldi, p.pool_ld = pool
+    def _stats_buf(self, rows, Cc, cols=2):
+        """[rows][cols][Cc] fp32 partial sums; the 64 rows behind them are the fold scratch of ryolo_bn_finalize / ryolo_bn_act_bwd (a buffer
+        without them is written past its end: this is the only place that sizes one)."""
+        return self.f32(rows + 64, cols, Cc)[:rows]
+
+    def _gemm_params(self, *args, **kw):
+        return P.gemm_params(*args, zeros=self.rt.zeros.data_ptr(), pipe=self.rt.gemm_pipe, **kw)
+
+    def _gemm(self, tape, *args, **kw):
+        """Emit one ryolo_conv_gemm launch (arguments: params.gemm_params).  For epi == EPI_STATS the partial-statistics buffer is sized by
+        the library's plan (one [2][Nout] row per M tile of the kernel it will run) and returned."""
+        p = self._gemm_params(*args, **kw)
         stats = None
-        if epi == S.EPI_STATS:
+        if p.epi == S.EPI_STATS:
             rows = S.I()
             hip.call("ryolo_conv_gemm_plan", p, rows, None)
-            stats = self.f32(rows.value + 64, 2, Nout)[:rows.value]       # +64 rows: fold scratch of ryolo_bn_finalize
+            stats = self._stats_buf(rows.value, p.Nout)
             p.stats = stats.data_ptr()
         self._call(tape, "ryolo_conv_gemm", p)
         return stats
 
     def _conv_geom(self, conv, x):
-        k, s = conv.kernel_size[0], conv.stride[0]
-        pad = conv.padding[0]
-        OH = (x.H + 2 * pad - k) // s + 1
-        OW = (x.W + 2 * pad - k) // s + 1
-        return k, s, pad, OH, OW
+        k, s, pad = conv.kernel_size[0], conv.stride[0], conv.padding[0]
+        return (k, s, pad) + P.conv_out(x.H, x.W, k, s, pad)
 
     def _dgrad(self, conv, pk, dy, dy_ptr, dy_cin, x, pool=None):
         """x.grad (=|+=) conv_transpose(dy).  dy: TRef-like geometry (N, OH, OW, ld).  pool = {"idx", "z"} of a MaxPool2d(2, 2) of the
@@ -518,18 +467,10 @@ class Graph:
             self._gemm(self.bwd, dy, dy_ptr, pk["wd"], cin, k * k, dy_cin, x.H // 2, x.W // 2, 1, classes, epi, x.gptr(), x.ld,
                        full=(2, 2, x.H, x.W))
 
-    def _wgrad(self, conv, dy, dy_ptr, cout_pad, x, x_ptr=None, dW=None):
-        k, s, pad, OH, OW = self._conv_geom(conv, x)
-        p = S.WgradParams()
-        p.dY, p.ldY, p.Cout, p.CoutPad = dy_ptr, dy.ld, conv.out_channels, cout_pad
-        p.X, p.NB, p.IH, p.IW, p.Cin, p.ldX = x_ptr or x.ptr(), x.N, x.H, x.W, conv.in_channels, x.ld
-        p.OH, p.OW, p.sh, p.sw = OH, OW, s, s
-        taps = _taps_fwd(k, pad)
-        p.ntaps = len(taps)
-        for i, (dh, dw, _) in enumerate(taps):
-            p.dh[i], p.dw[i] = dh, dw
-        p.dW = dW if dW is not None else self.rt.grad_ptr(conv.weight)
-        self._emit_wgrad(p, side=True)
+    def _wgrad(self, conv, dy, dy_ptr, cout_pad, x, dW=None):
+        k, s, pad = conv.kernel_size[0], conv.stride[0], conv.padding[0]
+        self._emit_wgrad(P.wgrad_params(dy, dy_ptr, conv.out_channels, cout_pad, x, x.ptr(), conv.in_channels, k, s, pad,
+                                        dW if dW is not None else self.rt.grad_ptr(conv.weight)), side=True)
 
     def _emit_wgrad(self, p, side=False):
         """side: the launch may run on the weight-gradient stream (see run()): nothing on the main stream reads what it writes (the
@@ -572,14 +513,36 @@ class Graph:
                 self._dgrad(conv, pk, y, y.gptr(), cout, x, pool=pool_grad if (pool_grad and pool_grad.get("idx") is not None) else None)
         return y, stats, backward
 
+    def _stem_fwd(self, pk, cout, epi, out, stats=None, coeffs=None, act=0):
+        p = P.stem_params(self.img.data_ptr(), self.B, self.Hin, self.Win, pk["wf"], cout, epi, out, stats, coeffs, act)
+        self._call(self.fwd, "ryolo_stem3x3_fwd", p)
+        self._img_structs.append(p)
+
+    def _bn_coeffs(self, bn, Cc, *, stats=None, M=None, tape=None, into=None, ld=None, c0=None):
+        """Emit the launch that fills a BatchNorm's [4][Cc] coefficient tensor (`into`, or a new one) and return it.  With `stats` (partial rows
+        of M samples; c0 / ld: the member's channel slice of shared rows): batch statistics, running-statistics update, and the layer's
+        num_batches_tracked joins the per-step count.  Without: running statistics, on `tape` (forward, or wprep for inference plans); c0 / ld
+        then place the member in a shared `into` of ld channels."""
+        co = into if into is not None else self.f32(4, Cc)
+        tape = self.fwd if tape is None else tape
+        bnp = (bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr())
+        if stats is not None:
+            name, chans = ("ryolo_bn_finalize", (Cc,)) if c0 is None else ("ryolo_bn_finalize_slice", (ld, c0, Cc))
+            self._call(tape, name, stats.data_ptr(), stats.shape[0], *chans, float(M), float(bn.eps), float(bn.momentum), *bnp, co.data_ptr())
+            self.rt.bn_counters.append(bn)
+        elif into is not None and c0 is not None:
+            self._call(tape, "ryolo_bn_eval_coeffs_slice", *bnp, float(bn.eps), Cc, co.data_ptr(), ld, c0)
+        else:
+            self._call(tape, "ryolo_bn_eval_coeffs", *bnp, float(bn.eps), Cc, co.data_ptr())
+        return co
+
     def stem_raw(self, conv, want_stats, fused=None):
         """First layer (Cin = 3).  3x3 stride-1 stems (yolov4 / yolov7) run DIRECTLY on the fp32 NCHW image (csrc/stem.hip); other
         shapes (yolov5's 6x6 stride 2) go through an explicit im2col + single-tap GEMM (K padded to a multiple of 32)."""
         rt = self.rt
         pk = rt.packed(conv)
         k, s, pad = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-        OH = (self.Hin + 2 * pad - k) // s + 1
-        OW = (self.Win + 2 * pad - k) // s + 1
+        OH, OW = P.conv_out(self.Hin, self.Win, k, s, pad)
         kp = pk["CinP"]
         cout = conv.out_channels
         y = fused[2] if fused else self.new(self.B, OH, OW, cout)
@@ -587,18 +550,8 @@ class Graph:
         if (k, s, pad, conv.in_channels, cout, kp) == (3, 1, 1, 3, 32, 32) and self.Win % 16 == 0 and self.B * 3 * self.Hin * self.Win < 2 ** 31:
             rows, wsb = S.I(), S.Z()
             hip.call("ryolo_stem3x3_plan", self.B, self.Hin, self.Win, cout, rows, wsb)
-            p = S.StemParams()
-            p.img, p.NB, p.H, p.W = self.img.data_ptr(), self.B, self.Hin, self.Win
-            p.wf, p.Cout, p.epi, p.out, p.ldC = pk["wf"].data_ptr(), cout, epi, y.ptr(), y.ld
-            stats = None
-            if epi == S.EPI_STATS:
-                stats = self.f32(rows.value + 64, 2, cout)[:rows.value]
-                p.stats = stats.data_ptr()
-            if fused:
-                co = fused[0]
-                p.scale, p.shift, p.act = co.data_ptr() + 2 * cout * 4, co.data_ptr() + 3 * cout * 4, fused[1]
-            self._call(self.fwd, "ryolo_stem3x3_fwd", p)
-            self._img_structs.append(p)
+            stats = self._stats_buf(rows.value, cout) if epi == S.EPI_STATS else None
+            self._stem_fwd(pk, cout, epi, y, stats, fused[0] if fused else None, fused[1] if fused else 0)
 
             def backward(need_dx=False, fuse=None):
                 """fuse = (dz TRef, coeffs [4][C], bco, act code): BatchNorm + activation backward applied inside the kernel (the raw
@@ -628,13 +581,7 @@ class Graph:
         def backward(need_dx=False):
             scratch = self.f32(cout, kp)
             self.bwd.append((lambda *_a: (scratch.zero_(), 0)[1], (), "zero_scratch"))
-            p = S.WgradParams()
-            p.dY, p.ldY, p.Cout, p.CoutPad = y.gptr(), y.ld, cout, cout
-            p.X, p.NB, p.IH, p.IW, p.Cin, p.ldX = col.ptr(), col.N, col.H, col.W, kp, col.ld
-            p.OH, p.OW, p.sh, p.sw, p.ntaps = OH, OW, 1, 1, 1
-            p.dh[0], p.dw[0] = 0, 0
-            p.dW = scratch.data_ptr()
-            self._emit_wgrad(p)
+            self._emit_wgrad(P.wgrad_params(y, y.gptr(), cout, cout, col, col.ptr(), kp, 1, 1, 0, scratch.data_ptr()))
             self._call(self.bwd, "ryolo_unpack_wgrad", scratch.data_ptr(), cout, 3, k * k, kp, rt.grad_ptr(conv.weight))
         return y, stats, backward
 
@@ -654,28 +601,12 @@ class Graph:
         hip.call("ryolo_stem3x3_plan", self.B, self.Hin, self.Win, cout, rows, None)
         z = out if out is not None else self.new(self.B, self.Hin, self.Win, cout)
         co = self.f32(4, cout)
-
-        def params(epi):
-            p = S.StemParams()
-            p.img, p.NB, p.H, p.W = self.img.data_ptr(), self.B, self.Hin, self.Win
-            p.wf, p.Cout, p.epi = pk["wf"].data_ptr(), cout, epi
-            self._img_structs.append(p)
-            return p
+        stats = None
         if self.batch_stats:
-            p0 = params(S.EPI_STATS)                      # out stays null: statistics only
-            stats = self.f32(rows.value + 64, 2, cout)[:rows.value]
-            p0.stats = stats.data_ptr()
-            self._call(self.fwd, "ryolo_stem3x3_fwd", p0)
-            self._call(self.fwd, "ryolo_bn_finalize", stats.data_ptr(), stats.shape[0], cout, float(z.M), float(bn.eps), float(bn.momentum),
-                       bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), co.data_ptr())
-            rt.bn_counters.append(bn)
-        else:
-            self._call(self.fwd, "ryolo_bn_eval_coeffs", bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                       bn.running_var.data_ptr(), float(bn.eps), cout, co.data_ptr())
-        p1 = params(S.EPI_AFFINE_ACT_R)
-        p1.out, p1.ldC = z.ptr(), z.ld
-        p1.scale, p1.shift, p1.act = co.data_ptr() + 2 * cout * 4, co.data_ptr() + 3 * cout * 4, actc
-        self._call(self.fwd, "ryolo_stem3x3_fwd", p1)
+            stats = self._stats_buf(rows.value, cout)
+            self._stem_fwd(pk, cout, S.EPI_STATS, None, stats)       # no output: statistics only
+        self._bn_coeffs(bn, cout, stats=stats, M=z.M, into=co)
+        self._stem_fwd(pk, cout, S.EPI_AFFINE_ACT_R, z, coeffs=co, act=actc)
         self.debug[id(conv)] = (z, z, None)
 
         def backward():
@@ -691,6 +622,28 @@ class Graph:
         return z
 
     # ------------------------------------------------------------------ Conv = conv -> BN -> act (+ residual)
+    def _bn_act_bwd(self, p, z, dys, bns, residual=None):
+        """Emit ryolo_bn_act_bwd for the forward block p: z's gradient -> the raw gradients `dys` (TRefs of y1[, y2]; none: statistics only,
+        the apply pass rides in the consumer), the residual's gradient and the gradients of the BatchNorm(s) `bns`.  Returns bco [3][C]."""
+        Cc = p.C
+        q = S.BnActParams()
+        C.memmove(C.byref(q), C.byref(p), C.sizeof(p))
+        nblk, rpb = S.I(), S.I()
+        hip.call("ryolo_bn_act_bwd_blocks", p.M, Cc, nblk, rpb)
+        # (two BatchNorms = RepConv: three partial columns, and bco is allocated after them — allocation order is part of the recorded plans)
+        bco = self.f32(3, Cc) if len(bns) == 1 else None
+        q.partial = self._stats_buf(nblk.value, Cc, 1 + len(bns)).data_ptr()
+        bco = self.f32(3, Cc) if bco is None else bco
+        q.dz, q.lddz = z.gptr(), z.ld
+        for n, dy in enumerate(dys, 1):
+            setattr(q, f"dy{n}", dy.gptr())
+            setattr(q, f"lddy{n}", dy.ld)
+        if residual is not None:
+            q.dres, q.lddres, q.dres_accum = residual.gptr(), residual.ld, residual.grad_write_mode()
+        grads = [self.rt.grad_ptr(t) for bn in bns for t in (bn.weight, bn.bias)] + [None, None]
+        self._call(self.bwd, "ryolo_bn_act_bwd", q, *grads[:4], bco.data_ptr(), 1 if self.frozen else 0)
+        return bco
+
     def conv_bn_act(self, conv, bn, act, x, out=None, residual=None, stem=False, pool_grad=None):
         """model/utils.py:6-32.  x None => stem on the staged input image.  Returns the activation TRef."""
         rt = self.rt
@@ -700,13 +653,10 @@ class Graph:
         cout = conv.out_channels
         if not train and residual is None:
             # inference: BatchNorm folded to scale/shift (running statistics) + activation inside the GEMM epilogue
-            co = self.f32(4, cout)
             # folded scale/shift depend on the weights only: their own tape, so a captured inference graph can leave them out
-            self._call(self.wprep, "ryolo_bn_eval_coeffs", bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                       bn.running_var.data_ptr(), float(bn.eps), cout, co.data_ptr())
-            k_, s_, pad_ = conv.kernel_size[0], conv.stride[0], conv.padding[0]
+            co = self._bn_coeffs(bn, cout, tape=self.wprep)
             H_, W_ = (self.Hin, self.Win) if stem else (x.H, x.W)
-            OH_, OW_ = (H_ + 2 * pad_ - k_) // s_ + 1, (W_ + 2 * pad_ - k_) // s_ + 1
+            OH_, OW_ = P.conv_out(H_, W_, conv.kernel_size[0], conv.stride[0], conv.padding[0])
             z = out if out is not None else self.new(self.B if stem else x.N, OH_, OW_, cout)
             fused = (co, actc, z)
             (self.stem_raw(conv, False, fused) if stem else self.conv_raw(conv, x, False, fused))
@@ -717,14 +667,7 @@ class Graph:
             if z is not None:
                 return z
         y, stats, conv_bwd = (self.stem_raw(conv, bstat) if stem else self.conv_raw(conv, x, bstat, pool_grad=pool_grad))
-        co = self.f32(4, cout)
-        if bstat:
-            self._call(self.fwd, "ryolo_bn_finalize", stats.data_ptr(), stats.shape[0], cout, float(y.M), float(bn.eps), float(bn.momentum),
-                       bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), co.data_ptr())
-            rt.bn_counters.append(bn)
-        else:
-            self._call(self.fwd, "ryolo_bn_eval_coeffs", bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                       bn.running_var.data_ptr(), float(bn.eps), cout, co.data_ptr())
+        co = self._bn_coeffs(bn, cout, stats=stats, M=y.M)
         z = out if out is not None else self.new(y.N, y.H, y.W, cout)
         assert z.C == cout and z.M == y.M
         self.debug[id(conv)] = (y, z, x)
@@ -736,21 +679,9 @@ class Graph:
         self._call(self.fwd, "ryolo_bn_act_fwd", p)
         if train:
             def backward():
-                bco = self.f32(3, cout)
-                q = S.BnActParams()
-                C.memmove(C.byref(q), C.byref(p), C.sizeof(p))
-                nblk, rpb = S.I(), S.I()
-                hip.call("ryolo_bn_act_bwd_blocks", y.M, cout, nblk, rpb)
-                partial = self.f32(nblk.value + 64, 2, cout)
-                q.dz, q.lddz = z.gptr(), z.ld
-                # direct stem: the apply pass moves into the weight-gradient kernel (its only consumer); here statistics only
+                # direct stem: the apply pass moves into the weight-gradient kernel (its only consumer); here statistics only (no dy1)
                 fuse_stem = stem and residual is None and getattr(conv_bwd, "can_fuse_bn", False) and rt.fuse_stem_bn
-                if not fuse_stem:
-                    q.dy1, q.lddy1 = y.gptr(), y.ld
-                if residual is not None:
-                    q.dres, q.lddres, q.dres_accum = residual.gptr(), residual.ld, residual.grad_write_mode()
-                q.partial = partial.data_ptr()
-                self._call(self.bwd, "ryolo_bn_act_bwd", q, rt.grad_ptr(bn.weight), rt.grad_ptr(bn.bias), None, None, bco.data_ptr(), 1 if self.frozen else 0)
+                bco = self._bn_act_bwd(p, z, [] if fuse_stem else [y], [bn], residual=residual)
                 if fuse_stem:
                     conv_bwd(need_dx=False, fuse=(z, co, bco, actc))
                 else:
@@ -788,8 +719,7 @@ class Graph:
             co = self.f32(4, ctot)
             off = 0
             for bn, cout in zip(bns, couts):
-                self._call(self.wprep, "ryolo_bn_eval_coeffs_slice", bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                           bn.running_var.data_ptr(), float(bn.eps), cout, co.data_ptr(), ctot, off)
+                self._bn_coeffs(bn, cout, tape=self.wprep, into=co, ld=ctot, c0=off)
                 off += cout
             z = TRef(outs[0].buf, outs[0].c0, ctot)
             self._gemm(self.fwd, x, x.ptr(), grp["wf"], ctot, k * k, cin, OH, OW, s_, taps, S.EPI_AFFINE_ACT, z.ptr(), z.ld, coeffs=co,
@@ -804,15 +734,7 @@ class Graph:
         zs, parts, off = [], [], 0
         for m, conv, bn, cout, out in zip(mods, convs, bns, couts, outs):
             ys = y.slice(off, cout)
-            co = self.f32(4, cout)
-            if bstat:
-                self._call(self.fwd, "ryolo_bn_finalize_slice", stats.data_ptr(), stats.shape[0], ctot, off, cout, float(y.M), float(bn.eps),
-                           float(bn.momentum), bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                           bn.running_var.data_ptr(), co.data_ptr())
-                rt.bn_counters.append(bn)
-            else:
-                self._call(self.fwd, "ryolo_bn_eval_coeffs", bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                           bn.running_var.data_ptr(), float(bn.eps), cout, co.data_ptr())
+            co = self._bn_coeffs(bn, cout, stats=stats, M=y.M, ld=ctot, c0=off)      # (frozen: stats is None, the member's own running statistics)
             z = out if out is not None else self.new(y.N, y.H, y.W, cout)
             assert z.C == cout and z.M == y.M
             self.debug[id(conv)] = (ys, z, x)
@@ -821,32 +743,14 @@ class Graph:
             p.z, p.ldz, p.M, p.C, p.act = z.ptr(), z.ld, y.M, cout, S.ACT[m.act]
             self._call(self.fwd, "ryolo_bn_act_fwd", p)
             zs.append(z)
-            parts.append((p, ys, z, bn, cout))
+            parts.append((p, ys, z, bn))
             off += cout
 
         def backward():
-            for p, ys, z, bn, cout in parts:
-                bco = self.f32(3, cout)
-                q = S.BnActParams()
-                C.memmove(C.byref(q), C.byref(p), C.sizeof(p))
-                nblk, rpb = S.I(), S.I()
-                hip.call("ryolo_bn_act_bwd_blocks", y.M, cout, nblk, rpb)
-                partial = self.f32(nblk.value + 64, 2, cout)
-                q.dz, q.lddz = z.gptr(), z.ld
-                q.dy1, q.lddy1 = ys.gptr(), ys.ld
-                q.partial = partial.data_ptr()
-                self._call(self.bwd, "ryolo_bn_act_bwd", q, rt.grad_ptr(bn.weight), rt.grad_ptr(bn.bias), None, None, bco.data_ptr(),
-                           1 if self.frozen else 0)
-            w = S.WgradParams()
-            w.dY, w.ldY, w.Cout, w.CoutPad = y.gptr(), y.ld, ctot, ctot
-            w.X, w.NB, w.IH, w.IW, w.Cin, w.ldX = x.ptr(), x.N, x.H, x.W, cin, x.ld
-            w.OH, w.OW, w.sh, w.sw = OH, OW, s_, s_
-            tp = _taps_fwd(k, pad)
-            w.ntaps = len(tp)
-            for i, (dh, dw, _) in enumerate(tp):
-                w.dh[i], w.dw[i] = dh, dw
-            w.dW, w.dW2, w.Cout1 = rt.grad_ptr(convs[0].weight), rt.grad_ptr(convs[1].weight), couts[0]
-            self._emit_wgrad(w, side=True)
+            for p, ys, z, bn in parts:
+                self._bn_act_bwd(p, z, [ys], [bn])
+            self._emit_wgrad(P.wgrad_params(y, y.gptr(), ctot, ctot, x, x.ptr(), cin, k, s_, pad, rt.grad_ptr(convs[0].weight),
+                                            rt.grad_ptr(convs[1].weight), couts[0]), side=True)
             self._dgrad(c0, {"wd": grp["wd"]}, y, y.gptr(), ctot, x)
         self._pending_bwd.append(backward)
         return zs
@@ -865,8 +769,7 @@ class Graph:
             cin = conv_a.in_channels
             coa, cob, co = self.f32(4, cout), self.f32(4, cout), self.f32(4, cout)
             for bn, c4 in ((bn_a, coa), (bn_b, cob)):
-                self._call(self.wprep, "ryolo_bn_eval_coeffs", bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                           bn.running_var.data_ptr(), float(bn.eps), cout, c4.data_ptr())
+                self._bn_coeffs(bn, cout, tape=self.wprep, into=c4)
             wfold = torch.empty((cout, 9, cin), dtype=BF16, device=self.adev)
             self.keep.append(wfold)
             self._call(self.wprep, "ryolo_repconv_fold", conv_a.weight.data_ptr(), conv_b.weight.data_ptr(), coa.data_ptr(), cob.data_ptr(),
@@ -879,13 +782,7 @@ class Graph:
         yb, sb, bwd_b = self.conv_raw(conv_b, x, bstat)
         coa, cob = self.f32(4, cout), self.f32(4, cout)
         for bn, st, co, y in ((bn_a, sa, coa, ya), (bn_b, sb, cob, yb)):
-            if bstat:
-                self._call(self.fwd, "ryolo_bn_finalize", st.data_ptr(), st.shape[0], cout, float(y.M), float(bn.eps), float(bn.momentum),
-                           bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), co.data_ptr())
-                rt.bn_counters.append(bn)
-            else:
-                self._call(self.fwd, "ryolo_bn_eval_coeffs", bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(),
-                           bn.running_var.data_ptr(), float(bn.eps), cout, co.data_ptr())
+            self._bn_coeffs(bn, cout, stats=st, M=y.M, into=co)
         z = self.new(ya.N, ya.H, ya.W, cout)
         p = S.BnActParams()
         p.y1, p.ld1, p.co1 = ya.ptr(), ya.ld, coa.data_ptr()
@@ -894,17 +791,7 @@ class Graph:
         self._call(self.fwd, "ryolo_bn_act_fwd", p)
         if train:
             def backward():
-                nblk, rpb = S.I(), S.I()
-                hip.call("ryolo_bn_act_bwd_blocks", ya.M, cout, nblk, rpb)
-                partial = self.f32(nblk.value + 64, 3, cout)
-                bco = self.f32(3, cout)
-                q = S.BnActParams()
-                C.memmove(C.byref(q), C.byref(p), C.sizeof(p))
-                q.dz, q.lddz = z.gptr(), z.ld
-                q.dy1, q.lddy1, q.dy2, q.lddy2 = ya.gptr(), ya.ld, yb.gptr(), yb.ld
-                q.partial = partial.data_ptr()
-                self._call(self.bwd, "ryolo_bn_act_bwd", q, rt.grad_ptr(bn_a.weight), rt.grad_ptr(bn_a.bias), rt.grad_ptr(bn_b.weight),
-                           rt.grad_ptr(bn_b.bias), bco.data_ptr(), 1 if self.frozen else 0)
+                self._bn_act_bwd(p, z, [ya, yb], [bn_a, bn_b])
                 bwd_a()
                 bwd_b()
             self._pending_bwd.append(backward)
@@ -915,8 +802,7 @@ class Graph:
         """grad_into: a dict handed earlier to the sibling 1x1 conv of the same input (conv_bn_act(..., pool_grad=grad_into)): this pool's
         backward is then NOT a launch of its own — the sibling's data-gradient store adds it (ConvGemmParams.pool_idx)."""
         pad = 0 if stride == 2 else k // 2
-        OH = (x.H + 2 * pad - k) // stride + 1
-        OW = (x.W + 2 * pad - k) // stride + 1
+        OH, OW = P.conv_out(x.H, x.W, k, stride, pad)
         z = out if out is not None else self.new(x.N, OH, OW, x.C)
         idx = torch.empty((x.N * OH * OW, x.C), dtype=torch.uint8, device=self.adev) if self.training else None
         self.keep.append(idx)
@@ -995,7 +881,7 @@ class Graph:
         och = 4 if getattr(rt.model, "mode", None) == "csl" else 5         # objectness element of a head row (lib/loss.py:216, :411)
         mptr = implicit_m.data_ptr() if implicit_m is not None else None
         sparse = self.training and _HEAD_SPARSE
-        fused = _HEAD_FUSED and rt.wgrad_lanes <= 1 and self._head_fused_ok(x, pk, cout, conv, x, attrs, och)
+        fused = _HEAD_FUSED and rt.wgrad_lanes <= 1 and self._head_fused_ok(conv, pk, x, attrs, och)
         if fused and implicit_a is not None and implicit_m is not None and _HEAD_FOLD_A:
             # ImplicitA rides in the bias (W (x + a) + b = W x + (b + W a)): no x + a tensor, and its gradient comes out of ryolo_head_wgrad_finish
             return self._head_fused(conv, pk, x, x, na, attrs, och, implicit_a, implicit_m, sparse, fold_a=True)
@@ -1028,49 +914,52 @@ class Graph:
         rec = dict(out=out, dout=None, preobj=preobj, och=och, xobj=xobj)
         self.heads.append(rec)
         if self.training:
-            dout = self.f32(x.N, na, x.H, x.W, attrs)
-            rec["dout"] = dout
-            dpre = torch.zeros((M, coutp), dtype=BF16, device=self.adev)       # pad columns stay zero
-            self.keep.append(dpre)
-            nblk = x.N * ((x.H * x.W + 127) // 128)
-            scratch = self.f32(max((nblk + 64) * 2 * cout, ((M + 255) // 256 + 64) * max(coutp, x.C)))
-
-            class _G:                      # geometry shim so dpre can be used as a gathered operand
-                N, H, W, ld = x.N, x.H, x.W, coutp
-                span_bytes = M * coutp * 2
+            finish_bwd, dpre, scratch, rows = self._head_bwd_prep(rec, conv, pk, x, na, attrs)
 
             def backward():
                 # dpre, the conv bias gradient (column sums of dpre) and the ImplicitM gradient in one pass over dout
-                self._call(self.bwd, "ryolo_head_finish_bwd", dout.data_ptr(), pre.data_ptr(), coutp, mptr, x.N, x.H, na, attrs,
-                           dpre.data_ptr(), coutp, rt.grad_ptr(conv.bias), rt.grad_ptr(implicit_m) if implicit_m is not None else None,
-                           scratch.data_ptr())
-                rec["dout_slot"] = len(self.bwd) - 1   # first argument (dout pointer) is patched per call when the caller's grad is usable as is
-                self._wgrad(conv, _G, dpre.data_ptr(), coutp, xin)
+                finish_bwd(pre.data_ptr(), mptr, rt.grad_ptr(conv.bias), rt.grad_ptr(implicit_m) if implicit_m is not None else None)
+                self._wgrad(conv, rows, dpre.data_ptr(), coutp, xin)
                 # ImplicitA: d(x + a)/dx = 1, so the data gradient is written straight into x's gradient (no buffer for xin's, no copy)
                 # and d/da is its column sum
-                self._dgrad(conv, pk, _G, dpre.data_ptr(), coutp, x)
+                self._dgrad(conv, pk, rows, dpre.data_ptr(), coutp, x)
                 if implicit_a is not None:
                     self._call(self.bwd, "ryolo_colsum_bf16", x.gptr(), x.ld, M, x.C, x.C, rt.grad_ptr(implicit_a), scratch.data_ptr())
             self._pending_bwd.append(backward)
         return out
 
-    def _head_fused_ok(self, xin, pk, cout, conv, x, attrs, och):
+    def _head_fused_ok(self, conv, pk, xin, attrs, och):
         """Does the library write this head in its final layout from the GEMM epilogue (ConvGemmParams.head_attrs)?"""
         if conv.kernel_size != (1, 1) or conv.stride != (1, 1) or attrs < 7:
             return False
-        p = S.ConvGemmParams()
-        p.A, p.NB, p.IH, p.IW, p.Cin, p.ldA = xin.ptr(), x.N, x.H, x.W, conv.in_channels, xin.ld
-        p.W, p.Nout, p.wtaps = pk["wf"].data_ptr(), cout, 1
-        p.OH, p.OW, p.sh, p.sw = x.H, x.W, 1, 1
-        p.oh_mul, p.ow_mul, p.OHf, p.OWf = 1, 1, x.H, x.W
-        p.nclasses = 1
-        _fill_class(p.cls[0], [(0, 0, 0)], 0, 0)
-        p.epi, p.pipe, p.head_attrs, p.head_och = S.EPI_F32_BIAS, self.rt.gemm_pipe, attrs, och
         try:
-            hip.call("ryolo_conv_gemm_plan", p, S.I(), S.I())
+            hip.call("ryolo_conv_gemm_plan", self._head_gemm(conv, pk, xin, attrs, och), S.I(), S.I())
         except RuntimeError:
             return False
         return True
+
+    def _head_gemm(self, conv, pk, xin, attrs, och, out=None, bias=None, mptr=None, xobj=None):
+        """ConvGemmParams of a detection head written in its final layout — with the destination pointers the block _head_fused launches,
+        without them the block _head_fused_ok asks the plan about."""
+        return self._gemm_params(xin, xin.ptr(), pk["wf"], conv.out_channels, 1, conv.in_channels, xin.H, xin.W, 1, [([(0, 0, 0)], 0, 0)],
+                                 S.EPI_F32_BIAS, out, attrs, bias=bias, head=(attrs, och, mptr, xobj))
+
+    def _head_bwd_prep(self, rec, conv, pk, x, na, attrs):
+        """What both head backwards share: the fp32 gradient map `dout` (rec["dout"]; the loss may hand its own in, set_head_grad), its bf16
+        row-major form `dpre` with the geometry to gather it, the reduction scratch, and the emitter of ryolo_head_finish_bwd(pre, ImplicitM,
+        bias gradient, ImplicitM gradient), which records the entry whose first argument set_head_grad patches."""
+        cout, coutp, M = conv.out_channels, pk["CoutP"], x.M
+        dout = rec["dout"] = self.f32(x.N, na, x.H, x.W, attrs)
+        dpre = torch.zeros((M, coutp), dtype=BF16, device=self.adev)       # pad columns stay zero
+        self.keep.append(dpre)
+        nblk = x.N * ((x.H * x.W + 127) // 128)
+        scratch = self.f32(max((nblk + 64) * 2 * cout, ((M + 255) // 256 + 64) * max(coutp, x.C)))
+
+        def finish_bwd(pre, mptr, dbias, dm):
+            self._call(self.bwd, "ryolo_head_finish_bwd", dout.data_ptr(), pre, coutp, mptr, x.N, x.H, na, attrs, dpre.data_ptr(), coutp, dbias, dm,
+                       scratch.data_ptr())
+            rec["dout_slot"] = len(self.bwd) - 1
+        return finish_bwd, dpre, scratch, P.Rows(x.N, x.H, x.W, coutp)
 
     def _head_fused(self, conv, pk, x, xin, na, attrs, och, implicit_a, implicit_m, sparse, fold_a=False):
         """r05: the head GEMM writes [B, na, gs, gs, attrs] itself — bias, ImplicitM and the permute in its epilogue, the compact objectness
@@ -1089,36 +978,25 @@ class Graph:
             fbias = self.f32(cout)
             self._call(self.fwd, "ryolo_head_bias_fold", conv.weight.data_ptr(), conv.bias.data_ptr(), aptr, cout, conv.in_channels, fbias.data_ptr())
             bias_ptr = fbias.data_ptr()
-        self._gemm(self.fwd, xin, xin.ptr(), pk["wf"], cout, 1, conv.in_channels, x.H, x.W, 1, [([(0, 0, 0)], 0, 0)], S.EPI_F32_BIAS,
-                   out.data_ptr(), attrs, bias=bias_ptr, head=(attrs, och, mptr, xobj.data_ptr() if xobj is not None else None))
+        self._call(self.fwd, "ryolo_conv_gemm", self._head_gemm(conv, pk, xin, attrs, och, out.data_ptr(), bias_ptr, mptr,
+                                                                xobj.data_ptr() if xobj is not None else None))
         rec = dict(out=out, dout=None, preobj=None, och=och, xobj=xobj)
         self.heads.append(rec)
         if self.training:
             if implicit_m is not None and pk.get("wd_scale") is None:
                 pk["wd_scale"] = implicit_m
                 rt._pack_table = None
-            dout = self.f32(x.N, na, x.H, x.W, attrs)
-            rec["dout"] = dout
-            dpre = torch.zeros((M, coutp), dtype=BF16, device=self.adev)       # pad columns stay zero
-            self.keep.append(dpre)
-            nblk = x.N * ((x.H * x.W + 127) // 128)
-            scratch = self.f32(max((nblk + 64) * 2 * cout, ((M + 255) // 256 + 64) * max(coutp, x.C)))
+            finish_bwd, dpre, scratch, rows = self._head_bwd_prep(rec, conv, pk, x, na, attrs)
             G = s = None
             if implicit_m is not None:
                 G = self.f32(cout, conv.in_channels, zero=True)                # (ryolo_head_wgrad_finish clears both again)
                 s = self.f32(cout, zero=True)
 
-            class _G:                      # geometry shim so dpre can be used as a gathered operand
-                N, H, W, ld = x.N, x.H, x.W, coutp
-                span_bytes = M * coutp * 2
-
             def backward():
                 # dpre = bf16(dout) and its column sums (the bias gradient, or s with ImplicitM) in one pass over dout
-                self._call(self.bwd, "ryolo_head_finish_bwd", dout.data_ptr(), None, coutp, None, x.N, x.H, na, attrs, dpre.data_ptr(), coutp,
-                           s.data_ptr() if s is not None else rt.grad_ptr(conv.bias), None, scratch.data_ptr())
-                rec["dout_slot"] = len(self.bwd) - 1
-                self._wgrad(conv, _G, dpre.data_ptr(), coutp, xin, dW=G.data_ptr() if G is not None else None)
-                self._dgrad(conv, pk, _G, dpre.data_ptr(), coutp, x)
+                finish_bwd(None, None, s.data_ptr() if s is not None else rt.grad_ptr(conv.bias), None)
+                self._wgrad(conv, rows, dpre.data_ptr(), coutp, xin, dW=G.data_ptr() if G is not None else None)
+                self._dgrad(conv, pk, rows, dpre.data_ptr(), coutp, x)
                 if implicit_m is not None:
                     self._call(self.bwd, "ryolo_head_wgrad_finish", G.data_ptr(), s.data_ptr(), conv.weight.data_ptr(), conv.bias.data_ptr(),
                                mptr, aptr, cout, conv.in_channels, rt.grad_ptr(conv.weight), rt.grad_ptr(conv.bias), rt.grad_ptr(implicit_m),

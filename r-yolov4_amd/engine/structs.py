@@ -10,6 +10,15 @@ EPI_RAW, EPI_STATS, EPI_AFFINE_ACT, EPI_F32_BIAS, EPI_ACCUM, EPI_AFFINE_ACT_R = 
 ACT = {"linear": 0, "mish": 1, "leaky": 2, "swish": 3}
 
 
+class KernelWord(int):
+    """The kernel word of ryolo_conv_gemm_plan (ryolo.h): family in bits 0-7; generic kernel: bit 8 = its 1x1 instantiation, bits 12-15 = tile
+    rows / 64; generic, patch and gemm256 kernels: bits 16-19 = tile columns / 32."""
+    family = property(lambda w: w & 0xff)
+    is_1x1 = property(lambda w: bool(w & 0x100))
+    tile_rows = property(lambda w: ((w >> 12) & 15) * 64)
+    tile_cols = property(lambda w: ((w >> 16) & 15) * 32)
+
+
 class TapClass(C.Structure):
     _fields_ = [("ntaps", I), ("oh_add", I), ("ow_add", I), ("dh", C.c_byte * MAX_TAPS), ("dw", C.c_byte * MAX_TAPS),
                 ("widx", C.c_byte * MAX_TAPS)]

@@ -4,7 +4,7 @@ import sys, os, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from ryolov4_amd import hip
-from ryolov4_amd.engine import structs as S
+from ryolov4_amd.engine import params as P, structs as S
 args = [int(a, 0) for a in sys.argv[1:]] + [None] * 8
 B, H, Cin, Cout, k, stride, pipe, reps = [a if a is not None else d for a, d in zip(args[:8], (8, 200, 128, 128, 3, 1, 1, 20))]
 epi = int(os.environ.get("EPI", "0"))
@@ -16,21 +16,9 @@ x = torch.randn(B * H * H, Cin, device=dev).to(torch.bfloat16)
 w = (torch.randn(Cout, k * k, Cin, device=dev) * 0.05).to(torch.bfloat16)
 y = torch.empty(B * OH * OH, Cout, dtype=torch.bfloat16, device=dev)
 zeros = torch.zeros(256, dtype=torch.uint8, device=dev)
-p = S.ConvGemmParams()
-p.A, p.NB, p.IH, p.IW, p.Cin, p.ldA = x.data_ptr(), B, H, H, Cin, Cin
-p.W, p.Nout, p.wtaps = w.data_ptr(), Cout, k * k
-p.OH, p.OW, p.sh, p.sw = OH, OH, stride, stride
-p.oh_mul, p.ow_mul, p.OHf, p.OWf = 1, 1, OH, OH
-p.nclasses = 1
-tc = p.cls[0]; tc.ntaps = k * k
-for r in range(k):
-    for s in range(k):
-        tc.dh[r * k + s], tc.dw[r * k + s], tc.widx[r * k + s] = r - pad, s - pad, r * k + s
-p.epi, p.out, p.ldC = epi, y.data_ptr(), Cout
-p.zeros, p.pipe = zeros.data_ptr(), pipe
-p.a_bytes, p.w_bytes = x.numel() * 2, w.numel() * 2
 co = torch.rand(4, Cout, device=dev) + 0.5                    # EPI=2: folded BatchNorm scale (row 2) / shift (row 3), SiLU
-p.scale, p.shift, p.act = co.data_ptr() + 2 * Cout * 4, co.data_ptr() + 3 * Cout * 4, int(os.environ.get("ACT", "3"))
+p = P.gemm_params(P.Rows(B, H, H, Cin), x.data_ptr(), w, Cout, k * k, Cin, OH, OH, stride, [(P._taps_fwd(k, pad), 0, 0)], epi, y.data_ptr(), Cout,
+                  zeros.data_ptr(), pipe, coeffs=co, act=int(os.environ.get("ACT", "3")))
 rows, kern = S.I(), S.I()
 try:
     hip.call("ryolo_conv_gemm_plan", p, rows, kern)

@@ -4,7 +4,7 @@ import sys, os, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from ryolov4_amd import hip
-from ryolov4_amd.engine import structs as S
+from ryolov4_amd.engine import params as P, structs as S
 args = [int(a, 0) for a in sys.argv[1:]] + [None] * 7
 B, H, Cin, Cout, k, stride, reps = [a if a is not None else d for a, d in zip(args[:7], (64, 100, 128, 128, 3, 1, 10))]
 dev = "cuda:0"
@@ -14,14 +14,7 @@ OH = (H + 2 * pad - k) // stride + 1
 x = torch.randn(B * H * H, Cin, device=dev).to(torch.bfloat16)
 dy = (torch.randn(B * OH * OH, Cout, device=dev) * 0.1).to(torch.bfloat16)
 dw = torch.zeros(Cout, Cin, k * k, device=dev)
-p = S.WgradParams()
-p.dY, p.ldY, p.Cout, p.CoutPad = dy.data_ptr(), Cout, Cout, Cout
-p.X, p.NB, p.IH, p.IW, p.Cin, p.ldX = x.data_ptr(), B, H, H, Cin, Cin
-p.OH, p.OW, p.sh, p.sw, p.ntaps = OH, OH, stride, stride, k * k
-for r in range(k):
-    for s in range(k):
-        p.dh[r * k + s], p.dw[r * k + s] = r - pad, s - pad
-p.dW = dw.data_ptr()
+p = P.wgrad_params(P.Rows(B, OH, OH, Cout), dy.data_ptr(), Cout, Cout, P.Rows(B, H, H, Cin), x.data_ptr(), Cin, k, stride, pad, dw.data_ptr())
 zeros = torch.zeros(256, dtype=torch.uint8, device=dev)
 if os.environ.get('W3', '1') == '1': p.zeros = zeros.data_ptr()
 sk, ws = S.I(), S.Z()
