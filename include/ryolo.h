@@ -493,6 +493,54 @@ int ryolo_tile_mark(const float* skey, const int64_t* order, const int64_t* keep
 int ryolo_tile_fuse(const float* cand, const int64_t* order, const int32_t* nsel, const int64_t* keep, const int32_t* num_keep,
                     const int32_t* owner, int nc, int64_t K, int64_t keep_stride, int64_t ld, int mode, int n_ens, float* fused, float* fkey,
                     ryolo_stream_t stream);
+/* Seam-aware merge (csrc/seam.hip; lib/tiled.py Seam(margin, cover, whole)): a window border cuts an object into a fragment that ends at
+ * the border, and the overlapping neighbour sees the same object whole.  Two rules around the NMS, which itself is unchanged; off unless
+ * asked for.  All arithmetic fp32, one operation per step, no FMA contraction.
+ *
+ * Slots and frames.  A slot is live when cls = cand[slot][6] satisfies 0 <= cls < nc (compared in fp32), c = (int)cls, and
+ * key[c][slot] > -inf.  Its entry is e = slot / mk (live needs e < nwin), its own window the entry's (x0, y0) and rate r from geom, and
+ * (Hr, Wr) = (win[e][1], win[e][2]) the resized extent of that rate.  Per live row (x, y, w, h, theta):
+ *   cs = |(float)cos((double)theta)|;  sn = |(float)sin((double)theta)|
+ *   ex = 0.5f * (cs*w + sn*h);  ey = 0.5f * (sn*w + cs*h)
+ *   X = x*r;  Y = y*r;  EX = ex*r;  EY = ey*r;  xl = X - EX;  xr = X + EX;  yt = Y - EY;  yb = Y + EY
+ * Cut bits, against the row's own window (a side on the border of the resized scene never cuts), x1 = x0 + S, y1 = y0 + S:
+ *   1 (L): x0 > 0  and xl <= x0 + margin        2 (R): x1 < Wr and xr >= x1 - margin
+ *   4 (T): y0 > 0  and yt <= y0 + margin        8 (B): y1 < Hr and yb >= y1 - margin
+ * Rule 1, "seen whole elsewhere" (whole = 1): a row with a cut bit is redundant (bit 16) when some window (vx, vy) of the same rate has
+ *   vx <= X < vx + S and vy <= Y < vy + S,   vx == 0 or xl > vx + margin,   vx + S >= Wr or xr < (vx + S) - margin,
+ *   vy == 0 or yt > vy + margin,   vy + S >= Hr or yb < (vy + S) - margin.
+ * Windows are the entries 0, nviews, 2 * nviews, ... (entries are window-major) and are ordered by rate (tile_plan): the windows of the
+ * row's rate are the run around its own window whose geom rate equals r; windows of another rate are not consulted.  The row's own
+ * window can never qualify (a cut side fails its own clearance).  Rule 1 trusts that the other window reported the object.
+ * flags uint8 [ld] = the row's bits, 0 for a dead slot.  key2 is [nc + 1][ld].  whole = 1: rows 0 .. nc - 1 = key with -inf at (c, slot)
+ * of every redundant row; they take key's place in the first ryolo_topk_desc of the merge and nothing else of the merge changes.
+ * whole = 0: only the cut bits are set and rows 0 .. nc - 1 are not written.  Row nc is set to -inf in both cases: it is the final key
+ * of the seam merge (what fkey is to the plain one: ryolo_tile_mark / ryolo_tile_fuse / ryolo_tile_seam_cover and the last
+ * ryolo_topk_desc take it as their fkey).  fkey is reset by the collect pass only, and marks of another keep set would survive in it;
+ * with a key of its own a seam merge neither sees the plain merge's marks nor leaves any, so the merges can follow each other on the
+ * same collected scene in any order.  counts int32 [2] is zeroed (both words) and counts[0] receives the number of redundant rows
+ * (integer atomics).  cand, key, win and geom are only read; key2 != key.  The window table is staged in LDS, 16 bytes per window:
+ * more than 4096 windows are unsupported.  Capturable: no allocation, no host read. */
+int ryolo_tile_seam_flags(const float* cand, const float* key, const int64_t* win, const float* geom, int64_t nwin, int nviews, int64_t mk,
+                          int64_t ld, int nc, int S, float margin, int whole, uint8_t* flags, float* key2, int32_t* counts,
+                          ryolo_stream_t stream);
+/* Rule 2, "covered fragment": behind ryolo_tile_mark or ryolo_tile_fuse, on the candidates' own geometry (under fusion the fused rows are
+ * not used).  Per class c, a and b range over the kept positions keep[c, 0 .. num_keep[c] - 1]; A and B are their rboxes rows as the NMS
+ * saw them (degrees, no class offset), area = w*h.  A kept a whose slot order[c, a] has a cut bit in flags is dropped when some kept
+ * b != a has area_b > area_a and cov >= cover, with
+ *   iou = the pair function of the NMS on (prep(A), prep(B)), the cut box first
+ *   s = area_a + area_b;  n = iou*s;  d1 = 1 + iou;  d = d1*area_a;  cov = n / d            (= intersection / area_a through the IoU)
+ * The decision depends on the keep set alone (a box that is itself dropped still counts as a b), so it is order-free and deterministic.
+ * A dropped a gets fkey[order[c, a]] = -inf (under fusion its cluster goes with it) and counts[1] is incremented (integer atomic;
+ * ryolo_tile_seam_flags zeroed it).  Pairs whose inflated circumscribed circles do not meet are rejected before the pair function; cover
+ * lies in [0.05, 1], far above the ~1e-10 artefacts the pair function can return for disjoint boxes.  A fragment absorbed by a whole box
+ * in the NMS has already entered the sums of ryolo_tile_fuse.  keep_stride <= K.  workspace: ryolo_tile_seam_workspace_bytes(nc, K).
+ * As in ryolo_tile_fuse the device tables are not trusted: a kept position outside [0, min(nsel[c], K)) or a slot outside [0, ld) is an
+ * empty box that is never cut and covers nothing; no access leaves the buffers.  Capturable: no allocation, no host read. */
+int ryolo_tile_seam_workspace_bytes(int nc, int64_t K, size_t* bytes);
+int ryolo_tile_seam_cover(const float* rboxes, const int64_t* order, const int32_t* nsel, const int64_t* keep, const int32_t* num_keep, int nc,
+                          int64_t K, int64_t keep_stride, const uint8_t* flags, int64_t ld, float cover, float* fkey, int32_t* counts, void* ws,
+                          size_t ws_bytes, ryolo_stream_t stream);
 /* order [>= num[0]] = ryolo_topk_desc of fkey, num [1] its selection count -> out [max_det, 7] = cand[order[j]] for j < num[0], zeros after */
 int ryolo_tile_emit(const float* cand, const int64_t* order, const int32_t* num, int64_t max_det, float* out, ryolo_stream_t stream);
 

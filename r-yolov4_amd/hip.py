@@ -63,6 +63,9 @@ _SIGNATURES = {
     "ryolo_resize_hsv_windows": [_P, _P, _I, _L, _P, _P, _P],
     "ryolo_scene_label_rows": [_P, _L, _P, _P, _I, ctypes.c_double, _P, _P],
     "ryolo_tile_fuse": [_P, _P, _P, _P, _P, _P, _I, _L, _L, _L, _I, _I, _P, _P, _P],
+    "ryolo_tile_seam_flags": [_P, _P, _P, _P, _L, _I, _L, _L, _I, _I, _F, _I, _P, _P, _P, _P],
+    "ryolo_tile_seam_workspace_bytes": [_I, _L, ctypes.POINTER(_Z)],
+    "ryolo_tile_seam_cover": [_P, _P, _P, _P, _P, _I, _L, _L, _P, _L, _F, _P, _P, _P, _Z, _P],
     "ryolo_anchor_workspace_bytes": [_L, ctypes.POINTER(_Z)],
     "ryolo_anchor_fitness": [_P, _L, _P, _I, ctypes.c_double, _P, _Z, _P, _P],
     "ryolo_anchor_evolve": [_P, _L, _P, _I, _P, _I, _I, ctypes.c_double, _P, _Z, _P, _P],

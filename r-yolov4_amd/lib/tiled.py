@@ -8,6 +8,7 @@ NMS — the workflow users of the reference rebuild by hand around detect.py, wh
     TiledDetector(model, size, overlap, batch, ...)(scene) -> Tensor[n, 7]          (x, y, w, h, theta_rad, score, cls) in scene pixels
     TiledDetector(..., views=("id", "hflip", "rot90"))                              every window also seen flipped / turned by 90 degrees (VIEWS)
     TiledDetector(..., fuse="box" | "wbf")                                          kept boxes absorb the boxes they suppressed (FUSE)
+    TiledDetector(..., seam=Seam(margin=2.0, cover=0.7, whole=True))                window-cut fragments seen whole elsewhere are dropped (Seam)
     TiledDetector.run_async(scene) -> (out [max_det, 7], num [1] int32)             the same with the count left on the device
     TiledDetector.detect_files(paths) -> iterator of (path, Tensor[n, 7])           scene i + 1 decoded / uploaded while scene i runs
     TiledDetector.iter_async(paths) -> iterator of (path, out, num)                 the same with the counts left on the device (lib/scene_eval.py)
@@ -34,6 +35,14 @@ with theta taken modulo pi and (w, h, theta) ~ (h, w, theta +- pi/2) resolved ag
 mean member score scaled by min(members, n) / n, n = len(rates) * len(views), so a box seen by one view of eight no longer keeps its
 full score.  The fused rows go to their own buffer (the candidates are only read) and the final order is taken over the fused scores.
 Two more launches per scene, no host read, and no allocation after a plan's first fused merge (which allocates the two buffers).  The arithmetic is defined in include/ryolo.h.
+
+Seams (seam=Seam(...), default None = the merge above, bit for bit, not one launch more; csrc/seam.hip): a window border cuts an object
+into a fragment that ends at the border, and the overlapping neighbour sees it whole; the NMS then lets a better-scoring fragment
+suppress the whole box, or keeps both.  ryolo_tile_seam_flags, in front of the selection, marks every candidate whose extent touches an
+interior border of its own window (within `margin` px) and, rule 1, takes those out of the selection's keys that another window of the
+same rate holds whole; ryolo_tile_seam_cover, behind ryolo_tile_mark / ryolo_tile_fuse, rule 2, drops kept cut boxes that a larger kept
+box of their class covers by at least `cover` of their area.  The NMS itself, the candidates and `key` are untouched; the buffers are
+allocated by a plan's first seam merge; `seam_counts` holds the two drop counts on the device.  The rules are defined in include/ryolo.h.
 """
 import math
 from collections import OrderedDict
@@ -74,6 +83,49 @@ def check_fuse(fuse):
     if fuse is None or (isinstance(fuse, str) and fuse in FUSE):
         return fuse
     raise ValueError(f"fuse must be None or one of {FUSE}, got {fuse!r}")
+
+
+class Seam:
+    """Seam handling of the merge (include/ryolo.h states the rules).  margin: a box side within `margin` window pixels of an interior
+    border of its own window counts as cut by it.  whole (rule 1): a cut box is left out of the merge when another window of the same
+    rate holds it clear of its own borders.  cover (rule 2; None = off): a kept cut box is dropped when a larger kept box of its class
+    covers at least this share of its area."""
+    __slots__ = ("margin", "cover", "whole")
+
+    def __init__(self, margin=2.0, cover=0.7, whole=True):
+        if isinstance(margin, bool) or not isinstance(margin, (int, float, np.integer, np.floating)) or not math.isfinite(margin) or margin < 0:
+            raise ValueError(f"Seam: margin must be a finite number >= 0 (window pixels), got {margin!r}")
+        if cover is not None and (isinstance(cover, bool) or not isinstance(cover, (int, float, np.integer, np.floating))
+                                  or not 0.05 <= cover <= 1):
+            raise ValueError(f"Seam: cover must be None or lie in [0.05, 1], got {cover!r}")
+        if not isinstance(whole, (bool, np.bool_)):
+            raise ValueError(f"Seam: whole must be a bool, got {whole!r}")
+        if not whole and cover is None:
+            raise ValueError("Seam: whole=False with cover=None leaves no rule; pass seam=None instead")
+        self.margin, self.cover, self.whole = float(margin), None if cover is None else float(cover), bool(whole)
+
+    def __repr__(self):
+        return f"Seam(margin={self.margin}, cover={self.cover}, whole={self.whole})"
+
+    def __eq__(self, other):
+        return isinstance(other, Seam) and (self.margin, self.cover, self.whole) == (other.margin, other.cover, other.whole)
+
+    def __hash__(self):
+        return hash((self.margin, self.cover, self.whole))
+
+
+def check_seam(seam):
+    """-> None or a Seam, validated; a dict of Seam's arguments is accepted."""
+    if seam is None:
+        return None
+    if isinstance(seam, dict):
+        try:
+            return Seam(**seam)
+        except TypeError as e:
+            raise ValueError(f"seam: {e}") from None
+    if isinstance(seam, Seam):
+        return Seam(seam.margin, seam.cover, seam.whole)                 # attributes set after construction are checked again
+    raise ValueError(f"seam must be None, a Seam or a dict of its arguments, got {seam!r}")
 
 
 # ------------------------------------------------------------------------------------------ window plan
@@ -197,6 +249,10 @@ class ScenePlan:
         # the first fused merge of the plan, so a detector that never fuses holds exactly the buffers it always held
         self.n_ens = len(det.rates) * len(self.views)
         self.owner = self.fused = None
+        # seam handling (merge_seam(..., seam=...)): cut / redundant bits by slot, the keys the first selection reads under rule 1 plus one
+        # row for the seam merge's own final key, the two drop counts and rule 2's workspace.  Allocated by the first seam merge of the plan, like the fusion buffers
+        self.nviews = len(self.views)
+        self.flags = self.key2 = self.seam_counts = self.seam_ws = None
 
     def cut(self, scene, g, dst):
         """Group g's entries of the scene at device address `scene` -> dst [batch, 3, size, size] (slots past the last entry untouched)."""
@@ -213,16 +269,42 @@ class ScenePlan:
         """Class-wise rotated NMS over every collected candidate, then the final order -> (out [max_det, 7], num [1]) on the device.
         fuse None: a kept box is emitted as it is.  "box" / "wbf": it absorbs the boxes it suppressed (ryolo_nms_owner + ryolo_tile_fuse
         in place of ryolo_tile_mark, the rows emitted from `fused`); the candidates are only read, so the modes can follow each other on
-        the same collected scene."""
-        fuse = check_fuse(fuse)
+        the same collected scene.  This is merge_seam without a seam: the launches it always issued, and no other."""
+        return self.merge_seam(merge_iou, gt_only, fuse, None)
+
+    def merge_seam(self, merge_iou, gt_only=True, fuse=None, seam=None):
+        """merge with the seam rules (merge's own parameter list is pinned by tests/test_tiled_fusion_cpu.py, so seam has a method of its
+        own).  seam None: merge, nothing more is launched.  A Seam (or a dict of its arguments): ryolo_tile_seam_flags in front of the selection, which
+        under rule 1 reads `key2` (the keys without the cut rows another window holds whole), and under rule 2 ryolo_tile_seam_cover behind
+        ryolo_tile_mark / ryolo_tile_fuse (kept cut rows that a larger kept box covers leave the final order).  `seam_counts` int32 [2]
+        holds the rows the two rules dropped in this merge, on the device.  A seam merge marks its kept slots in a key of its own (the
+        last row of `key2`, reset per merge), not in `fkey`: merges with and without seam can follow each other on the same collected
+        scene, and seam=None afterwards is the plain result bit for bit.  The window table `win` must hold the scene's rows
+        (TiledDetector uploads it per scene); the candidates and `key` are only read."""
+        fuse, seam = check_fuse(fuse), check_seam(seam)
         nc, Kc, Kf, st = self.nc, self.Kc, self.Kf, hip.stream()
-        hip.call("ryolo_topk_desc", hip.ptr(self.key), nc, self.ld, Kc, hip.ptr(self.skey), hip.ptr(self.order), hip.ptr(self.nsel), hip.ptr(self.sort_ws),
+        key, fkey = self.key, self.fkey
+        if seam is not None:
+            if self.flags is None:
+                dev, need = self.cand.device, hip._Z()
+                hip.call("ryolo_tile_seam_workspace_bytes", nc, Kc, need)
+                self.flags = torch.empty(self.ld, dtype=torch.uint8, device=dev)
+                self.seam_counts = torch.empty(2, dtype=torch.int32, device=dev)
+                self.seam_ws = torch.empty(max(need.value, 16), dtype=torch.uint8, device=dev)
+                self.key2 = torch.empty((nc + 1, self.ld), dtype=torch.float32, device=dev)
+            hip.call("ryolo_tile_seam_flags", hip.ptr(self.cand), hip.ptr(self.key), hip.ptr(self.win), hip.ptr(self.geom), self.T, self.nviews,
+                     self.mk, self.ld, nc, self.size, seam.margin, 1 if seam.whole else 0, hip.ptr(self.flags),
+                     hip.ptr(self.key2), hip.ptr(self.seam_counts), st)
+            if seam.whole:
+                key = self.key2
+            fkey = self.key2[nc]                                         # the seam merge's own final key (include/ryolo.h)
+        hip.call("ryolo_topk_desc", hip.ptr(key), nc, self.ld, Kc, hip.ptr(self.skey), hip.ptr(self.order), hip.ptr(self.nsel), hip.ptr(self.sort_ws),
                  self.sort_ws.numel(), st)
         hip.call("ryolo_tile_merge_gather", hip.ptr(self.cand), hip.ptr(self.skey), hip.ptr(self.order), nc, Kc, hip.ptr(self.rboxes), st)
         hip.call("ryolo_nms_rotated_batched", hip.ptr(self.rboxes), hip.ptr(self.nsel), nc, Kc, merge_iou, 1 if gt_only else 0, Kc,
                  hip.ptr(self.nms_ws), self.nms_ws.numel(), hip.ptr(self.keep), Kc, hip.ptr(self.nkeep), st)
         if fuse is None:
-            hip.call("ryolo_tile_mark", hip.ptr(self.skey), hip.ptr(self.order), hip.ptr(self.keep), hip.ptr(self.nkeep), nc, Kc, Kc, hip.ptr(self.fkey), st)
+            hip.call("ryolo_tile_mark", hip.ptr(self.skey), hip.ptr(self.order), hip.ptr(self.keep), hip.ptr(self.nkeep), nc, Kc, Kc, hip.ptr(fkey), st)
             rows = self.cand
         else:
             if self.fused is None:
@@ -231,9 +313,13 @@ class ScenePlan:
             hip.call("ryolo_nms_owner", hip.ptr(self.nsel), nc, Kc, hip.ptr(self.nms_ws), self.nms_ws.numel(), hip.ptr(self.keep), Kc,
                      hip.ptr(self.nkeep), hip.ptr(self.owner), st)
             hip.call("ryolo_tile_fuse", hip.ptr(self.cand), hip.ptr(self.order), hip.ptr(self.nsel), hip.ptr(self.keep), hip.ptr(self.nkeep),
-                     hip.ptr(self.owner), nc, Kc, Kc, self.ld, FUSE.index(fuse), self.n_ens, hip.ptr(self.fused), hip.ptr(self.fkey), st)
+                     hip.ptr(self.owner), nc, Kc, Kc, self.ld, FUSE.index(fuse), self.n_ens, hip.ptr(self.fused), hip.ptr(fkey), st)
             rows = self.fused
-        hip.call("ryolo_topk_desc", hip.ptr(self.fkey), 1, self.ld, Kf, hip.ptr(self.fskey), hip.ptr(self.forder), hip.ptr(self.num), hip.ptr(self.sort_ws),
+        if seam is not None and seam.cover is not None:
+            hip.call("ryolo_tile_seam_cover", hip.ptr(self.rboxes), hip.ptr(self.order), hip.ptr(self.nsel), hip.ptr(self.keep), hip.ptr(self.nkeep),
+                     nc, Kc, Kc, hip.ptr(self.flags), self.ld, seam.cover, hip.ptr(fkey), hip.ptr(self.seam_counts), hip.ptr(self.seam_ws),
+                     self.seam_ws.numel(), st)
+        hip.call("ryolo_topk_desc", hip.ptr(fkey), 1, self.ld, Kf, hip.ptr(self.fskey), hip.ptr(self.forder), hip.ptr(self.num), hip.ptr(self.sort_ws),
                  self.sort_ws.numel(), st)
         hip.call("ryolo_tile_emit", hip.ptr(rows), hip.ptr(self.forder), hip.ptr(self.num), self.max_det, hip.ptr(self.out), st)
         return self.out, self.num
@@ -264,10 +350,11 @@ class TiledDetector:
     len(views) (weighted box fusion).  The arithmetic is defined in include/ryolo.h (ryolo_tile_fuse)."""
 
     def __init__(self, model, size=1024, overlap=200, batch=8, conf_thres=0.1, iou_thres=0.4, merge_iou=None, rates=(1.0,), max_nms=5000,
-                 max_det=5000, gt_only=True, views=("id",), fuse=None):
+                 max_det=5000, gt_only=True, views=("id",), fuse=None, seam=None):
         rates = tuple(float(r) for r in rates)
         views = check_views(views)
         self.fuse = check_fuse(fuse)                                     # read per scene, like views and rates
+        self.seam = check_seam(seam)                                     # read per scene too
         tile_plan(size, size, size, overlap, rates)                      # argument validation
         if int(batch) < 1:
             raise ValueError(f"TiledDetector: batch must be >= 1, got {batch}")
@@ -318,6 +405,7 @@ class TiledDetector:
     # ---- the device pipeline of one scene
     def _enqueue(self, placed):
         fuse = check_fuse(self.fuse)                                     # a bad mode set on the detector fails before anything is launched
+        seam = check_seam(self.seam)
         H, W = placed.H, placed.W
         p = self.plan(H, W)
         st = hip.stream()
@@ -341,7 +429,7 @@ class TiledDetector:
             p.cut(scene, g, run.static_input)
             run.graph.replay()
             p.collect(run.post_plan.out, run.post_plan.num, g)
-        return p.merge(self.merge_iou, self.gt_only, fuse)
+        return p.merge_seam(self.merge_iou, self.gt_only, fuse, seam)
 
     # ---- public
     def run_async(self, scene):
