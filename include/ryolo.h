@@ -146,6 +146,54 @@ int ryolo_dota_match(const float* dets, const int32_t* num, int64_t max_det, con
                      const float* iouv, int niou, unsigned char* status, float* conf, float* pcls, int64_t cap, int64_t* cursor,
                      int32_t* overflow, int64_t* npos, void* workspace, size_t workspace_bytes, ryolo_stream_t stream);
 
+/* The error breakdown of ONE full scene, in ryolo_scene_match's launch shape and with its inputs (lib/scene_errors.py;
+ * tests/scene_errors_ref.py restates it in numpy): why the scene's mAP is what it is.  dets / num / max_det / labels [nl,6] / cls_off /
+ * nl / nc / cap / cursor / overflow: as for ryolo_scene_match; dets is only read.  Scalars, float32 by value: t_fg, t_bg with
+ * 0 <= t_bg < t_fg (foreground / background IoU), conf_thres, and the size edges e0 <= e1 as label areas in px^2 (RYOLO_ERR_ARG
+ * otherwise, NaN included).
+ * IoU is ryolo_scene_match's: theta of both as theta / 3.14159274f * 180.f, the pair function of the NMS, 0 for boxes whose inflated
+ * circumscribed circles do not meet.  Every comparison with a threshold is "above" (>): an IoU equal to a threshold is not above it.
+ * Per detection i < n = min(max(*num, 0), max_det):
+ *   active(i) = score_i >= conf_thres (a NaN score is inactive)
+ *   same(i)   = (s_iou, s_t): the first maximum over the labels of detection i's own class — best(i) of ryolo_scene_match; none
+ *               (-1, -1) for a class that is not an integer in [0, nc) (NaN included) or that has no label
+ *   other(i)  = (o_iou, o_t): the first maximum, in row order, over the label rows in [cls_off[0], cls_off[nc]) (clamped to [0, nl])
+ *               that are outside detection i's class range; for a detection with an invalid class these are all of them; none: (-1, -1)
+ *   a_iou(i)  = with s_t >= 0, the larger of IoU((x_i, y_i, w_i, h_i, theta_L), label s_t) and IoU((x_i, y_i, h_i, w_i, theta_L),
+ *               label s_t), theta_L the angle of label s_t (prepared exactly as the label's own): the detection turned to the label's
+ *               angle, the second box resolving (w, h, theta) ~ (h, w, theta +- pi/2); -1 otherwise
+ *   owner(t)  = the SMALLEST active i with s_t == t and s_iou > t_fg
+ * code[i], the first that applies:   0 BELOW  not active
+ *                                    1 TP     s_iou > t_fg and owner(s_t) == i
+ *                                    2 DUP    s_iou > t_fg (an earlier detection owns the label)
+ *                                    3 CLS    o_iou > t_fg (right place, wrong class)
+ *                                    4 ANG    s_iou > t_bg and a_iou > t_fg (right place and size, wrong angle)
+ *                                    5 LOC    s_iou > t_bg
+ *                                    6 BOTH   o_iou > t_bg
+ *                                    7 BKG    otherwise
+ * status of label row t, the first that applies:  0 FOUND t has an owner;  1 CONFUSED some detection with code CLS has o_t == t;
+ *   2 MISLOCATED some detection with code ANG or LOC has s_t == t;  3 MISSED otherwise.  Size bucket of a label:
+ *   (w*h >= e0) + (w*h >= e1) in float32.  The class of a label row is its cls column; a row whose cls is not an integer in [0, nc)
+ *   is counted nowhere.
+ * Rows behind the cursor (cap each): code bytes; conf = score, pcls = cls, ocls = the cls column of label o_t or -1; s_iou, o_iou,
+ * a_iou.  Histograms, int64 on the device, zeroed by the caller before the first scene, added to:
+ *   det_hist [nc+1][8]     row = the predicted class (row nc: a class that is not an integer in [0, nc)), column = code
+ *   cm [nc+1][nc+1]        cm[true][pred]: TP -> [c][c]; CLS -> [class(o_t)][c]; DUP, ANG, LOC, BOTH, BKG -> [nc][c]; a label that is
+ *                          not FOUND -> [class(t)][nc]; detections with an invalid class and BELOW rows are not counted
+ *   lab_hist [nc][3][4]    class, size bucket, status
+ * With cur = *cursor the rows cur .. cur + n - 1 are written and the cursor advances by n; if cur + n > cap NOTHING moves — no row, no
+ * histogram, no cursor — and *overflow = 1.  max_det == 0 is legal: only the label side moves, every label MISSED.
+ * Launches: label prologue (prepared labels, owner / cover word reset), one wave per detection (ONE pass over the rows of every class
+ * keeping both first maxima, the two turned IoUs on two lanes, one atomicMin), a thread per detection (code, row, atomicOr on the cover
+ * word, histograms counted per workgroup in LDS and flushed once), a thread per label (status, histogram), the cursor.  Integer
+ * atomics only: deterministic; no host read; capturable.  Every index that comes from data (cls_off entries, the classes, *num, the
+ * stored s_t / o_t) is clamped or checked as in ryolo_scene_match.  nc <= 256 (RYOLO_ERR_UNSUPPORTED beyond). */
+int ryolo_scene_errors_workspace_bytes(int64_t max_det, int64_t nl, size_t* bytes);
+int ryolo_scene_errors(const float* dets, const int32_t* num, int64_t max_det, const float* labels, const int32_t* cls_off, int64_t nl, int nc,
+                       float t_fg, float t_bg, float conf_thres, float e0, float e1, unsigned char* code, float* conf, float* pcls, float* ocls,
+                       float* s_iou, float* o_iou, float* a_iou, int64_t* det_hist, int64_t* cm, int64_t* lab_hist, int64_t cap, int64_t* cursor,
+                       int32_t* overflow, void* workspace, size_t workspace_bytes, ryolo_stream_t stream);
+
 /* VOC AP from the accumulated rows of ryolo_dota_match, on the device.  status [n][niou] bytes (1 TP, 2 ignored, anything else FP),
  * conf / pred_cls [n] fp32, npos [nc] int64 (device), grid11 [11] float64 on the device (np.arange(0., 1.1, 0.1) from the host).
  * Per class c and threshold k: the rows of class c by confidence descending (equal confidence: the earlier row first), rows with

@@ -964,3 +964,233 @@ extern "C" int ryolo_ap_voc(const unsigned char* status, const float* conf, cons
     RY_CHECK_LAUNCH();
     return RY_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ full-scene error breakdown
+// Why a scene's mAP is what it is (include/ryolo.h: ryolo_scene_errors states the rule): every detection gets one code — true positive,
+// duplicate, right place / wrong class, wrong angle only, mislocated, both, background — and every label one status.  The launch shape is
+// the skeleton's, with a matcher of its own: the wave of a detection scans the labels of EVERY class once and keeps two running first
+// maxima (own class, other classes), then two lanes compute the IoUs of the detection turned to its best label's angle, then lane 0 claims
+// the label.  Histograms are counted block-locally in LDS and flushed once per workgroup with integer atomics; the confusion matrix follows
+// from the same counts except for its CLS cells, which are rare.  Nothing is read back, nothing allocates, every run gives the same bits.
+#define ERR_CODES 8
+#define ERR_BUCKETS 3
+#define ERR_STATUSES 4
+enum { ERR_BELOW = 0, ERR_TP, ERR_DUP, ERR_CLS, ERR_ANG, ERR_LOC, ERR_BOTH, ERR_BKG };
+
+// a class column as a row of the histograms: the integer in [0, nc), or -1
+__device__ __forceinline__ int class_index(float cls, int nc)
+{
+    if (!(cls >= 0.f && cls < (float)nc)) return -1;                  // NaN fails both
+    const int c = (int)cls;
+    return (float)c == cls && c >= 0 && c < nc ? c : -1;
+}
+
+__device__ __forceinline__ void hist_add(int64_t* __restrict__ cell, int v)
+{
+    atomicAdd(reinterpret_cast<unsigned long long*>(cell), (unsigned long long)v);
+}
+
+__global__ __launch_bounds__(256) void errors_prep_kernel(const float* __restrict__ labels, int64_t nl, int nc, BoxPrep* __restrict__ prep,
+                                                          int32_t* __restrict__ owner, int32_t* __restrict__ cover, int32_t* __restrict__ lcls)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nl) return;
+    SceneRule::prep_label(labels + t * 6, prep[t]);
+    owner[t] = INT_MAX;
+    cover[t] = 0;
+    lcls[t] = class_index(labels[t * 6], nc);
+}
+
+__global__ __launch_bounds__(64 * MATCH_WAVES) void errors_best_kernel(const float* __restrict__ dets, const int32_t* __restrict__ num, int64_t max_det,
+                                                                       const float* __restrict__ labels, const BoxPrep* __restrict__ prep,
+                                                                       const int32_t* __restrict__ cls_off, int64_t nl, int nc, float t_fg,
+                                                                       float conf_thres, float* __restrict__ s_iou, int32_t* __restrict__ s_t,
+                                                                       float* __restrict__ o_iou, int32_t* __restrict__ o_t,
+                                                                       float* __restrict__ a_iou, int32_t* __restrict__ owner)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * MATCH_WAVES + (threadIdx.x >> 6);
+    if (i >= det_count(num, max_det)) return;                         // wave-uniform
+    const float* pr = dets + i * 7;
+    const float box[5] = {pr[0], pr[1], pr[2], pr[3], pr[4]};
+    const float score = pr[5];
+    int64_t lo, hi;
+    class_range(pr[6], cls_off, nc, nl, lo, hi);
+    int64_t g0 = cls_off[0], g1 = cls_off[nc];                        // every class's rows, clamped as class_range clamps
+    g0 = g0 < 0 ? 0 : (g0 > nl ? nl : g0);
+    g1 = g1 < g0 ? g0 : (g1 > nl ? nl : g1);
+    const int64_t from = lo < hi && lo < g0 ? lo : g0, to = lo < hi && hi > g1 ? hi : g1;     // [g0, g1) with a good table
+    float si = -1.f, oi = -1.f;
+    int st = -1, ot = -1;
+    BoxPrep D;
+    SceneRule::prep_det(box, D);
+    for (int64_t t = from + lane; t < to; t += 64) {
+        const bool mine = t >= lo && t < hi;
+        if (!mine && (t < g0 || t >= g1)) continue;
+        const float v = SceneRule::iou(D, prep[t]);
+        if (mine) { if (v > si) { si = v; st = (int)t; } }
+        else if (v > oi) { oi = v; ot = (int)t; }
+    }
+    wave_first_max(si, st);
+    wave_first_max(oi, ot);
+    float ai = -1.f;
+    if (st >= 0 && st < nl) {                                         // wave-uniform: lane 0 the box as written, lane 1 with w and h swapped
+        const bool swap = lane & 1;
+        const float turned[5] = {box[0], box[1], swap ? box[3] : box[2], swap ? box[2] : box[3], labels[(int64_t)st * 6 + 5]};
+        BoxPrep A;
+        SceneRule::prep_rad(turned, A);
+        const float v = SceneRule::iou(A, prep[st]);
+        const float w = __shfl_xor(v, 1, 64);
+        ai = w > v ? w : v;
+    }
+    if (lane == 0) {
+        s_iou[i] = si;
+        s_t[i] = st;
+        o_iou[i] = oi;
+        o_t[i] = ot;
+        a_iou[i] = ai;
+        if (score >= conf_thres && st >= 0 && st < nl && si > t_fg) atomicMin(&owner[st], (int)i);
+    }
+}
+
+// a thread per detection: its code, its row behind the cursor, the cover word of the label it points at, the histograms
+__global__ __launch_bounds__(256) void errors_emit_kernel(const float* __restrict__ dets, const int32_t* __restrict__ num, int64_t max_det,
+                                                          const float* __restrict__ labels, int64_t nl, int nc, float t_fg, float t_bg,
+                                                          float conf_thres, const float* __restrict__ s_iou, const int32_t* __restrict__ s_t,
+                                                          const float* __restrict__ o_iou, const int32_t* __restrict__ o_t,
+                                                          const float* __restrict__ a_iou, const int32_t* __restrict__ owner,
+                                                          int32_t* __restrict__ cover, const int32_t* __restrict__ lcls,
+                                                          unsigned char* __restrict__ code, float* __restrict__ conf, float* __restrict__ pcls,
+                                                          float* __restrict__ ocls, float* __restrict__ r_s, float* __restrict__ r_o,
+                                                          float* __restrict__ r_a, int64_t* __restrict__ det_hist, int64_t* __restrict__ cm,
+                                                          int64_t cap, const int64_t* __restrict__ cursor)
+{
+    __shared__ int h[(MAP_MAX_CLASSES + 1) * ERR_CODES];
+    const int cells = (nc + 1) * ERR_CODES;
+    for (int k = threadIdx.x; k < cells; k += 256) h[k] = 0;
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t n = det_count(num, max_det), cur = *cursor;
+    if (!rows_fit(cur, n, cap)) return;                               // uniform over the grid: nothing moves
+    if (i < n) {
+        const float score = dets[i * 7 + 5], cls = dets[i * 7 + 6];
+        const float si = s_iou[i], oi = o_iou[i], ai = a_iou[i];
+        const int st = s_t[i], ot = o_t[i];
+        const bool has_s = st >= 0 && st < nl, has_o = ot >= 0 && ot < nl;
+        int c = ERR_BKG;
+        if (!(score >= conf_thres)) c = ERR_BELOW;
+        else if (has_s && si > t_fg) c = owner[st] == (int)i ? ERR_TP : ERR_DUP;
+        else if (has_o && oi > t_fg) c = ERR_CLS;
+        else if (has_s && si > t_bg) c = ai > t_fg ? ERR_ANG : ERR_LOC;
+        else if (has_o && oi > t_bg) c = ERR_BOTH;
+        const int64_t r = cur + i;
+        code[r] = (unsigned char)c;
+        conf[r] = score;
+        pcls[r] = cls;
+        ocls[r] = has_o ? labels[(int64_t)ot * 6] : -1.f;
+        r_s[r] = si;
+        r_o[r] = oi;
+        r_a[r] = ai;
+        if (c == ERR_CLS) atomicOr(&cover[ot], 1);
+        if (c == ERR_ANG || c == ERR_LOC) atomicOr(&cover[st], 2);
+        const int pc = class_index(cls, nc);
+        atomicAdd(&h[(pc < 0 ? nc : pc) * ERR_CODES + c], 1);
+        if (c == ERR_CLS && pc >= 0) {
+            const int lc = lcls[ot];
+            if (lc >= 0) hist_add(&cm[(int64_t)lc * (nc + 1) + pc], 1);
+        }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < cells; k += 256) {
+        const int v = h[k];
+        if (v == 0) continue;
+        hist_add(&det_hist[k], v);
+        const int pc = k / ERR_CODES, c = k % ERR_CODES;
+        if (pc == nc || c == ERR_BELOW || c == ERR_CLS) continue;     // the other cells of cm follow from the counts
+        hist_add(&cm[(int64_t)(c == ERR_TP ? pc : nc) * (nc + 1) + pc], v);
+    }
+}
+
+// a thread per label: its status from the owner and the cover word, counted by class and size
+__global__ __launch_bounds__(256) void errors_label_kernel(const float* __restrict__ labels, int64_t nl, int nc, float e0, float e1,
+                                                           const int32_t* __restrict__ num, int64_t max_det, const int32_t* __restrict__ owner,
+                                                           const int32_t* __restrict__ cover, const int32_t* __restrict__ lcls,
+                                                           int64_t* __restrict__ lab_hist, int64_t* __restrict__ cm, int64_t cap,
+                                                           const int64_t* __restrict__ cursor)
+{
+    __shared__ int h[MAP_MAX_CLASSES * ERR_BUCKETS * ERR_STATUSES];
+    const int cells = nc * ERR_BUCKETS * ERR_STATUSES;
+    for (int k = threadIdx.x; k < cells; k += 256) h[k] = 0;
+    __syncthreads();
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (!rows_fit(*cursor, det_count(num, max_det), cap)) return;     // uniform over the grid
+    if (t < nl) {
+        const int lc = lcls[t];
+        if (lc >= 0) {
+            const int cv = cover[t];
+            const int s = owner[t] != INT_MAX ? 0 : ((cv & 1) ? 1 : ((cv & 2) ? 2 : 3));
+            const float area = labels[t * 6 + 3] * labels[t * 6 + 4];
+            const int b = (area >= e0 ? 1 : 0) + (area >= e1 ? 1 : 0);
+            atomicAdd(&h[(lc * ERR_BUCKETS + b) * ERR_STATUSES + s], 1);
+        }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < cells; k += 256) {
+        const int v = h[k];
+        if (v == 0) continue;
+        hist_add(&lab_hist[k], v);
+        if (k % ERR_STATUSES != 0) hist_add(&cm[(int64_t)(k / (ERR_BUCKETS * ERR_STATUSES)) * (nc + 1) + nc], v);
+    }
+}
+
+// workspace:  prep [nl] | owner [nl] | cover [nl] | lcls [nl] | s_iou, s_t, o_iou, o_t, a_iou [max_det] each
+static size_t errors_workspace_bytes(int64_t max_det, int64_t nl)
+{
+    return ry_align256((size_t)nl * sizeof(BoxPrep)) + 3 * ry_align256((size_t)nl * 4) + 5 * ry_align256((size_t)max_det * 4) + 256;
+}
+
+extern "C" int ryolo_scene_errors_workspace_bytes(int64_t max_det, int64_t nl, size_t* bytes)
+{
+    if (!bytes || max_det < 0 || nl < 0) return RY_ERR_ARG;
+    *bytes = errors_workspace_bytes(max_det, nl);
+    return RY_OK;
+}
+
+extern "C" int ryolo_scene_errors(const float* dets, const int32_t* num, int64_t max_det, const float* labels, const int32_t* cls_off, int64_t nl,
+                                  int nc, float t_fg, float t_bg, float conf_thres, float e0, float e1, unsigned char* code, float* conf,
+                                  float* pcls, float* ocls, float* s_iou, float* o_iou, float* a_iou, int64_t* det_hist, int64_t* cm,
+                                  int64_t* lab_hist, int64_t cap, int64_t* cursor, int32_t* overflow, void* ws, size_t ws_bytes,
+                                  hipStream_t stream)
+{
+    if (max_det < 0 || nl < 0 || nc < 1 || cap < 0) return RY_ERR_ARG;
+    if (!(t_bg >= 0.f && t_bg < t_fg) || conf_thres != conf_thres || !(e0 <= e1)) return RY_ERR_ARG;     // NaN fails each
+    if (nc > MAP_MAX_CLASSES || max_det >= INT_MAX || nl >= INT_MAX) return RY_ERR_UNSUPPORTED;
+    if (!cls_off || !cursor || !overflow || !num || !ws || !det_hist || !cm || !lab_hist || (nl > 0 && !labels)) return RY_ERR_ARG;
+    if (max_det > 0 && (!dets || !code || !conf || !pcls || !ocls || !s_iou || !o_iou || !a_iou)) return RY_ERR_ARG;
+    if (ws_bytes < errors_workspace_bytes(max_det, nl)) return RY_ERR_WORKSPACE;
+    unsigned char* base = reinterpret_cast<unsigned char*>(ws);
+    BoxPrep* prep = ws_take<BoxPrep>(base, (size_t)nl * sizeof(BoxPrep));
+    int32_t* owner = ws_take<int32_t>(base, (size_t)nl * 4);
+    int32_t* cover = ws_take<int32_t>(base, (size_t)nl * 4);
+    int32_t* lcls = ws_take<int32_t>(base, (size_t)nl * 4);
+    float* w_s = ws_take<float>(base, (size_t)max_det * 4);
+    int32_t* w_st = ws_take<int32_t>(base, (size_t)max_det * 4);
+    float* w_o = ws_take<float>(base, (size_t)max_det * 4);
+    int32_t* w_ot = ws_take<int32_t>(base, (size_t)max_det * 4);
+    float* w_a = ws_take<float>(base, (size_t)max_det * 4);
+    if (nl > 0)
+        hipLaunchKernelGGL(errors_prep_kernel, dim3((unsigned)ry_cdiv(nl, 256)), dim3(256), 0, stream, labels, nl, nc, prep, owner, cover, lcls);
+    if (max_det > 0) {
+        hipLaunchKernelGGL(errors_best_kernel, dim3((unsigned)ry_cdiv(max_det, MATCH_WAVES)), dim3(64 * MATCH_WAVES), 0, stream, dets, num, max_det,
+                           labels, prep, cls_off, nl, nc, t_fg, conf_thres, w_s, w_st, w_o, w_ot, w_a, owner);
+        hipLaunchKernelGGL(errors_emit_kernel, dim3((unsigned)ry_cdiv(max_det, 256)), dim3(256), 0, stream, dets, num, max_det, labels, nl, nc, t_fg,
+                           t_bg, conf_thres, w_s, w_st, w_o, w_ot, w_a, owner, cover, lcls, code, conf, pcls, ocls, s_iou, o_iou, a_iou, det_hist, cm,
+                           cap, cursor);
+    }
+    if (nl > 0)
+        hipLaunchKernelGGL(errors_label_kernel, dim3((unsigned)ry_cdiv(nl, 256)), dim3(256), 0, stream, labels, nl, nc, e0, e1, num, max_det, owner,
+                           cover, lcls, lab_hist, cm, cap, cursor);
+    hipLaunchKernelGGL(match_advance_kernel<SceneRule>, dim3(1), dim3(64), 0, stream, num, max_det, cap, cursor, overflow, SceneRule::Positives{});
+    RY_CHECK_LAUNCH();
+    return RY_OK;
+}

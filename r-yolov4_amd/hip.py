@@ -47,6 +47,8 @@ _SIGNATURES = {
     "ryolo_scene_match": [_P, _P, _L, _P, _P, _L, _I, _P, _I, _P, _P, _P, _L, _P, _P, _P, _Z, _P],
     "ryolo_dota_match_workspace_bytes": [_L, _L, _I, ctypes.POINTER(_Z)],
     "ryolo_dota_match": [_P, _P, _L, _P, _P, _L, _I, _P, _I, _P, _P, _P, _L, _P, _P, _P, _P, _Z, _P],
+    "ryolo_scene_errors_workspace_bytes": [_L, _L, ctypes.POINTER(_Z)],
+    "ryolo_scene_errors": [_P, _P, _L, _P, _P, _L, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _Z, _P],
     "ryolo_ap_voc_workspace_bytes": [_L, _I, _I, ctypes.POINTER(_Z)],
     "ryolo_ap_voc": [_P, _P, _P, _L, _P, _I, _I, _I, _P, _P, _Z, _P, _P, _P],
     "ryolo_to_tensor":[_P, _I, _I, _I, _P, _P, _P],
