@@ -1,5 +1,7 @@
-/* ryolo_params.h — POD parameter blocks of the libryolo_hip.so C ABI (plain C; mirrored with ctypes in
- * r-yolov4_amd/engine/structs.py and size-checked at load time through ryolo_struct_sizes()). */
+/* ryolo_params.h — POD parameter blocks and device-table records of the libryolo_hip.so C ABI.  Plain C, and the only statement of
+ * these layouts: r-yolov4_amd/abi.py reads this file into the ctypes classes (it understands integer #defines, scalar typedefs and
+ * `typedef struct X { ... } X;` with plain, comma-declared and array fields — no bit-fields, unions or nested definitions), and the
+ * library's own sizeof (ryolo_struct_sizes, ryolo_*_bytes) is compared at load time. */
 #ifndef RYOLO_PARAMS_H
 #define RYOLO_PARAMS_H
 #include <stddef.h>
@@ -161,5 +163,57 @@ typedef struct LossParams {
                               // ryolo_head_finish_fwd_obj leaves it; the objectness pass then reads 4 bytes per cell instead of one strided element
                               // of every row (= the whole map through the cache).  Must hold exactly the head maps' values.
 } LossParams;
+
+/* ---- records of the device tables the data side uploads (datasets/augment.py); ryolo_*_bytes report their sizeof ---- */
+
+/* ryolo_paste_rects: one `canvas[dy:dy+h, dx:dx+w] = src[sy:sy+h, sx:sx+w]` */
+typedef struct PasteRect {
+    int64_t src_off;             // byte offset of the source image in the pool
+    int src_w;                   // source row pitch in pixels
+    int sx, sy, dx, dy, w, h;
+    int canvas;                  // index of the destination canvas in the batch
+} PasteRect;
+
+/* ryolo_resize_hsv_batch: an SH x SW image of the pool -> NH x NW in the staging pool; interp 0 = INTER_LINEAR, 1 = INTER_AREA, 2 = copy;
+ * lut >= 0: index of this image's hsv tables.  WindowItem extends it by the window. */
+typedef struct ResizeItem {
+    int64_t src_off, dst_off;    // byte offsets into the source pool / the staging pool
+    int SH, SW, NH, NW;
+    int interp, lut;
+} ResizeItem;
+
+/* ryolo_resize_hsv_windows: ResizeItem of the cut (its source size is c x c) + where the cut lies in which scene */
+typedef struct WindowItem {
+    int64_t src_off, dst_off;    // byte offsets of the SCENE in the pool / of the result in the staging pool
+    int SH, SW;                  // the scene
+    int NH, NW;
+    int interp, lut;
+    int x0, y0, c;               // the window, scene pixels; may hang over any border (x0, y0 < 0 included)
+    int pad_;
+} WindowItem;
+
+/* ryolo_paste_prepare / _pixels / _labels: one pasted object */
+typedef struct PasteItem {
+    int64_t src_off;             // byte offset of the source SCENE in the pool
+    int SH, SW;                  // the scene
+    int slot;                    // canvas of the batch
+    float cls;
+    float quad[8];               // the source label, scene pixels
+    double M[6];                 // scene -> canvas (affine, row major 2 x 3)
+    double Minv[6];              // canvas -> scene
+} PasteItem;
+
+/* ryolo_label_stage / ryolo_scene_label_rows: one label of a placed source image */
+typedef struct LabelRow {
+    float poly[8];               // as parsed from the label file
+    float cls;
+    int slot;                    // image slot of the batch (column 0 of the result)
+    float w0, h0;                // original image size; 0: labels are already normalised (normalized_labels)
+    float w1, h1;                // size after load_image's resize
+    float bx1, bx2, by1, by2;    // `boarder` of load_target (source-image coordinates); bx2 < 0: no filter
+    float padw, padh;
+    float cx1, cx2, cy1, cy2;    // mosaic-9 crop window on the 3s canvas; cx2 < 0: none.  The origin (cx1, cy1) is subtracted afterwards
+    int mat;                     // index into the warp matrices, -1: none
+} LabelRow;
 
 #endif /* RYOLO_PARAMS_H */

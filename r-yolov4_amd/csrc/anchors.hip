@@ -22,9 +22,6 @@
 #define AN_THREADS 256
 #define KM_THREADS 64
 
-extern "C" int ryolo_sort_workspace_bytes(int rows, int64_t n_sorted, size_t* bytes);
-extern "C" int ryolo_argsort_desc(const float* scores, int64_t N, int64_t* order, void* ws, size_t ws_bytes, hipStream_t stream);
-
 // ------------------------------------------------------------------------------------------------ reach
 // csrc/loss.hip, cand_test: gw = tg[4] * fg, rw = gw / aw, max(rw, 1 / rw) < 4 on both sides; modes != 0 also |cos(theta - anchor angle)| >
 // 0.866.  The image index is not looked at (the loss drops rows whose index is outside the batch).

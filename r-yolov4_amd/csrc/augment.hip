@@ -12,14 +12,8 @@
 // load_mosaic / load_mosaic9 / mixup ran); warp and hsv restate OpenCV (third-party, absent here, version un-pinned by the reference):
 // "parity unpinned" — checked only against this build's own numpy restatement (oracle/ref_data.py).
 #include "common.h"
-#include "augment_px.h"     // load_px2, warp_bilinear_px, area_fast_scales, hsv_lut_pixel, area_axis, ResizeItem, LabelRow
-
-struct PasteRect {               // one `canvas[dy:dy+h, dx:dx+w] = src[sy:sy+h, sx:sx+w]`
-    int64_t src_off;             // byte offset of the source image in the pool
-    int src_w;                   // source row pitch in pixels
-    int sx, sy, dx, dy, w, h;
-    int canvas;                  // index of the destination canvas in the batch
-};
+#include "augment_px.h"     // load_px2, warp_bilinear_px, area_fast_scales, hsv_lut_pixel, area_axis
+// (PasteRect, ResizeItem and LabelRow, the records of the tables below: include/ryolo_params.h)
 
 // `first` (optional, [ncanvas + 1]): the rectangles of canvas b are rects[first[b] .. first[b + 1]) — the batch assembler emits them canvas by
 // canvas.  Without it every thread had to walk the whole table: ~370 rectangles x 190 M canvas pixels per batch of 64 mosaics = 20.6 ms, two
@@ -201,7 +195,7 @@ __global__ __launch_bounds__(256) void letterbox_kernel(const uint8_t* __restric
 // cv::ResizeArea_: per axis a leading partial cell, whole cells of weight 1 / cellWidth, a trailing partial cell; weights and sums in
 // float, cvRound at the end), 2 = copy (r == 1: the reference skips cv2.resize).  lut >= 0: the three 256-entry tables of hsv() for this
 // image (lib/augmentations.py:8-21) are applied to the resized pixel before it is stored (resize, then hsv in place: same result).
-// The item record is ResizeItem (augment_px.h).
+// The item record is ResizeItem (ryolo_params.h).
 __global__ __launch_bounds__(256) void resize_hsv_batch_kernel(const uint8_t* __restrict__ pool, const ResizeItem* __restrict__ items,
                                                                const uint8_t* __restrict__ luts, uint8_t* __restrict__ stage)
 {

@@ -75,14 +75,6 @@ __device__ __forceinline__ void area_fast_scales(int SH, int SW, int NH, int NW,
     iy = fast ? ry : 0;
 }
 
-// One row of ryolo_resize_hsv_batch's table (augment.hip): an SH x SW image of the pool -> NH x NW in the staging pool; interp 0 = INTER_LINEAR,
-// 1 = INTER_AREA, 2 = copy; lut >= 0: index of this image's hsv tables.  scene.hip's WindowItem extends it by the window.
-struct ResizeItem {
-    int64_t src_off, dst_off;    // byte offsets into the source pool / the staging pool
-    int SH, SW, NH, NW;
-    int interp, lut;
-};
-
 // divtab (optional, LDS): [0..255] = OpenCV's sdiv_table, [256..511] = hdiv_table180 — the two double-precision divisions per pixel as table
 // reads (what cv::cvtColor's 8-bit BGR2HSV does itself); same integers as the expressions below
 __device__ __forceinline__ void hsv_lut_pixel(int& b, int& g, int& r, const uint8_t* __restrict__ lut, const int* divtab = nullptr)
@@ -143,15 +135,3 @@ __device__ __forceinline__ AreaAxis area_axis(int d, int dn, int sn)
     a.whi = (float)(fmin(fmin(f2 - s2, 1.0), cell) / cell);
     return a;
 }
-
-struct LabelRow {
-    float poly[8];               // as parsed from the label file
-    float cls;
-    int slot;                    // image slot of the batch (column 0 of the result)
-    float w0, h0;                // original image size; 0: labels are already normalised (normalized_labels)
-    float w1, h1;                // size after load_image's resize
-    float bx1, bx2, by1, by2;    // `boarder` of load_target (source-image coordinates); bx2 < 0: no filter
-    float padw, padh;
-    float cx1, cx2, cy1, cy2;    // mosaic-9 crop window on the 3s canvas; cx2 < 0: none.  The origin (cx1, cy1) is subtracted afterwards
-    int mat;                     // index into the warp matrices, -1: none
-};

@@ -40,7 +40,8 @@ static inline int ry_max_dynamic_lds(RyLdsAttr& st, const void* fn, int bytes)
 }
 
 // ---- bf16 <-> f32 (round-to-nearest-even), device side -------------------------------------------------
-#include "ryolo_params.h"   // bf16_t + POD parameter blocks
+#include "ryolo.h"          // every entry point's declaration, so that the compiler holds each definition against it; through
+                            // ryolo_params.h: bf16_t, the POD parameter blocks and the device-table records
 
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((unsigned)v) << 16); }
 // fp32 -> bf16, round-to-nearest-even: gfx950 has a packed hardware convert (v_cvt_pk_bf16_f32); clang emits exactly that

@@ -15,16 +15,7 @@
 // Built with -ffp-contract=off like scene.hip: the fp64 clip and the edge tests are compared bit for bit.
 #include "common.h"
 #include "augment_px.h"
-
-struct PasteItem {
-    int64_t src_off;             // byte offset of the source SCENE in the pool
-    int SH, SW;                  // the scene
-    int slot;                    // canvas of the batch
-    float cls;
-    float quad[8];               // the source label, scene pixels
-    double M[6];                 // scene -> canvas (affine, row major 2 x 3)
-    double Minv[6];              // canvas -> scene
-};
+// (PasteItem, the record of the item table: include/ryolo_params.h)
 
 #define PASTE_FILL 114
 #define PASTE_TW 32              // tile of the pixel kernel: 32 x 8 pixels, one per thread

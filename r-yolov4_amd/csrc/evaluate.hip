@@ -315,9 +315,6 @@ static inline T* ws_take(unsigned char*& base, size_t bytes)
     return p;
 }
 
-extern "C" int ryolo_sort_workspace_bytes(int batch, int64_t n, size_t* bytes);
-extern "C" int ryolo_argsort_desc(const float* scores, int64_t N, int64_t* order, void* ws, size_t ws_bytes, hipStream_t stream);
-
 static inline size_t ap_rows(int64_t n) { return (size_t)(n > 0 ? n : 1); }
 
 // Both AP workspaces begin  sort workspace | order [n]:  the size checks and the bytes of that head ...

@@ -9,15 +9,7 @@
 // Built with -ffp-contract=off like augment.hip: the float sums of the area resize and the fp64 clip are compared bit for bit.
 #include "common.h"
 #include "augment_px.h"
-
-struct WindowItem {              // ResizeItem of the cut (its source size is c x c) + where the cut lies in which scene
-    int64_t src_off, dst_off;    // byte offsets of the SCENE in the pool / of the result in the staging pool
-    int SH, SW;                  // the scene
-    int NH, NW;
-    int interp, lut;
-    int x0, y0, c;               // the window, scene pixels; may hang over any border (x0, y0 < 0 included)
-    int pad_;
-};
+// (WindowItem, the record of ryolo_resize_hsv_windows' table, and LabelRow: include/ryolo_params.h)
 
 #define SCENE_FILL 114
 

@@ -29,9 +29,9 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from .. import hip
+from .. import abi, hip
 
-_I, _L, _P = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
+_I = ctypes.c_int
 
 
 class ImagePool:
@@ -292,37 +292,9 @@ def warp_matrix(shape, a, s, tx, ty, border=(0, 0)):
 
 
 # ------------------------------------------------------------------------------------------------ tables -> device
-class _Rect(ctypes.Structure):
-    _fields_ = [("src_off", _L), ("src_w", _I), ("sx", _I), ("sy", _I), ("dx", _I), ("dy", _I), ("w", _I), ("h", _I), ("canvas", _I)]
-
-
-class _ResizeItem(ctypes.Structure):
-    _fields_ = [("src_off", _L), ("dst_off", _L), ("SH", _I), ("SW", _I), ("NH", _I), ("NW", _I), ("interp", _I), ("lut", _I)]
-
-
-class _WindowItem(ctypes.Structure):      # csrc/scene.hip: _ResizeItem of a window's c x c cut + where the cut lies in its scene (SH, SW)
-    _fields_ = [("src_off", _L), ("dst_off", _L), ("SH", _I), ("SW", _I), ("NH", _I), ("NW", _I), ("interp", _I), ("lut", _I), ("x0", _I), ("y0", _I),
-                ("c", _I), ("pad_", _I)]
-
-
-class _PasteItem(ctypes.Structure):       # csrc/copypaste.hip: one pasted object (PASTE_ITEM_DTYPE is the same record for numpy)
-    _fields_ = [("src_off", _L), ("SH", _I), ("SW", _I), ("slot", _I), ("cls", ctypes.c_float), ("quad", ctypes.c_float * 8),
-                ("M", ctypes.c_double * 6), ("Minv", ctypes.c_double * 6)]
-
-
-class _LabelRow(ctypes.Structure):
-    _fields_ = [("poly", ctypes.c_float * 8), ("cls", ctypes.c_float), ("slot", _I), ("w0", ctypes.c_float), ("h0", ctypes.c_float),
-                ("w1", ctypes.c_float), ("h1", ctypes.c_float), ("bx1", ctypes.c_float), ("bx2", ctypes.c_float), ("by1", ctypes.c_float),
-                ("by2", ctypes.c_float), ("padw", ctypes.c_float), ("padh", ctypes.c_float), ("cx1", ctypes.c_float), ("cx2", ctypes.c_float),
-                ("cy1", ctypes.c_float), ("cy2", ctypes.c_float), ("mat", _I)]
-
-
-LABEL_ROW_DTYPE = np.dtype([("poly", np.float32, 8), ("cls", np.float32), ("slot", np.int32), ("w0", np.float32), ("h0", np.float32),
-                            ("w1", np.float32), ("h1", np.float32), ("bx1", np.float32), ("bx2", np.float32), ("by1", np.float32),
-                            ("by2", np.float32), ("padw", np.float32), ("padh", np.float32), ("cx1", np.float32), ("cx2", np.float32),
-                            ("cy1", np.float32), ("cy2", np.float32), ("mat", np.int32)])
-PASTE_ITEM_DTYPE = np.dtype([("src_off", np.int64), ("SH", np.int32), ("SW", np.int32), ("slot", np.int32), ("cls", np.float32),
-                             ("quad", np.float32, 8), ("M", np.float64, 6), ("Minv", np.float64, 6)])
+# the records of the device tables, as include/ryolo_params.h defines them (PasteRect, ResizeItem, WindowItem, PasteItem, LabelRow)
+_Rect, _ResizeItem, _WindowItem, _PasteItem, _LabelRow = (abi.STRUCTS[n] for n in ("PasteRect", "ResizeItem", "WindowItem", "PasteItem", "LabelRow"))
+LABEL_ROW_DTYPE, PASTE_ITEM_DTYPE = np.dtype(_LabelRow), np.dtype(_PasteItem)      # the same records for numpy: C offsets and itemsize
 INTERP_LINEAR, INTERP_AREA, INTERP_COPY = 0, 1, 2
 _checked = False
 
@@ -337,10 +309,6 @@ def _check_layouts():
         hip.call(name, n)
         if n.value != ctypes.sizeof(t):
             raise RuntimeError(f"ryolov4_amd: struct layout mismatch for {t.__name__}: C {n.value} vs ctypes {ctypes.sizeof(t)}")
-    if LABEL_ROW_DTYPE.itemsize != ctypes.sizeof(_LabelRow):
-        raise RuntimeError("ryolov4_amd: LABEL_ROW_DTYPE drifted from LabelRow")
-    if PASTE_ITEM_DTYPE.itemsize != ctypes.sizeof(_PasteItem):
-        raise RuntimeError("ryolov4_amd: PASTE_ITEM_DTYPE drifted from PasteItem")
     _checked = True
 
 

@@ -64,12 +64,6 @@ def _check_wh(wh, what):
     return wh.contiguous()
 
 
-def _ws(name, n, dev):
-    need = S.Z()
-    hip.call(name, n, need)
-    return torch.empty(max(need.value, 16), dtype=torch.uint8, device=dev), need.value
-
-
 def _stats(st, n):
     """stats tensor (int64 [4] on the host; element 0 holds a double) -> dict."""
     return dict(fitness=float(st[:1].view(torch.float64)[0]), reached=int(st[1]), passes=int(st[2]), accepted=int(st[3]),
@@ -80,9 +74,9 @@ def fitness_device(wh, k, thr=4.0):
     """-> stats int64 [4] on the device ([0] = the fitness, a double; reached labels; anchor passes; 0) of anchor set k [K, 2]."""
     wh = _check_wh(wh, "anchor_fitness")
     k = k.to(device=wh.device, dtype=torch.float32).reshape(-1, 2).contiguous()
-    ws, nb = _ws("ryolo_anchor_workspace_bytes", wh.shape[0], wh.device)
+    ws = hip.workspace("ryolo_anchor_workspace_bytes", wh.shape[0], device=wh.device)
     st = torch.empty(4, dtype=torch.int64, device=wh.device)
-    hip.call("ryolo_anchor_fitness", hip.ptr(wh), wh.shape[0], hip.ptr(k), k.shape[0], float(thr), hip.ptr(ws), nb, hip.ptr(st), hip.stream())
+    hip.call("ryolo_anchor_fitness", hip.ptr(wh), wh.shape[0], hip.ptr(k), k.shape[0], float(thr), hip.ptr(ws), ws.numel(), hip.ptr(st), hip.stream())
     return st
 
 
@@ -101,10 +95,10 @@ def evolve_device(wh, k, v, thr=4.0):
     if v.dtype != torch.float32 or v.dim() != 4 or v.shape[2] != K or v.shape[3] != 2 or not 1 <= v.shape[1] <= 16:
         raise ValueError("anchor_evolve: v must be float32 [G, 1 <= C <= 16, K, 2]")
     v = v.contiguous()
-    ws, nb = _ws("ryolo_anchor_workspace_bytes", wh.shape[0], wh.device)
+    ws = hip.workspace("ryolo_anchor_workspace_bytes", wh.shape[0], device=wh.device)
     st = torch.empty(4, dtype=torch.int64, device=wh.device)
     hip.call("ryolo_anchor_evolve", hip.ptr(wh), wh.shape[0], hip.ptr(k), K, hip.ptr(v) if v.shape[0] else None, v.shape[0], v.shape[1],
-             float(thr), hip.ptr(ws), nb, hip.ptr(st), hip.stream())
+             float(thr), hip.ptr(ws), ws.numel(), hip.ptr(st), hip.stream())
     return k, st
 
 
@@ -121,9 +115,9 @@ def kmeans_device(wh, k, iters=30, start=None, want_assign=False):
     else:
         cen = start.to(device=dev, dtype=torch.float32).reshape(-1, 2).contiguous().clone()
     assign = torch.empty(n, dtype=torch.int32, device=dev) if want_assign and int(iters) > 0 else None      # (no iteration: no assignment)
-    ws, nb = _ws("ryolo_anchor_kmeans_workspace_bytes", n, dev)
+    ws = hip.workspace("ryolo_anchor_kmeans_workspace_bytes", n, device=dev)
     hip.call("ryolo_anchor_kmeans", hip.ptr(wh), n, hip.ptr(cen), cen.shape[0], int(iters), 1 if start is None else 0, hip.ptr(assign),
-             hip.ptr(ws), nb, hip.stream())
+             hip.ptr(ws), ws.numel(), hip.stream())
     return (cen, assign) if want_assign else cen
 
 

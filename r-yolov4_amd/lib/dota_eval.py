@@ -93,9 +93,7 @@ class DotaEvaluator(_Evaluator):
             n_pred_d = torch.empty(nc, dtype=torch.int64, device=self.device)
             grid = torch.empty(11, dtype=torch.float64, device=self.device)
             _h2d(grid, GRID11)
-            need = hip._Z()
-            hip.call("ryolo_ap_voc_workspace_bytes", n, T, nc, need)
-            ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            ws = hip.workspace("ryolo_ap_voc_workspace_bytes", n, T, nc, device=self.device)
             hip.call("ryolo_ap_voc", hip.ptr(status), hip.ptr(conf), hip.ptr(pcls), n, hip.ptr(npos_d), nc, T, METRICS[self.metric], hip.ptr(grid),
                      hip.ptr(ws), ws.numel(), hip.ptr(ap_d), hip.ptr(n_pred_d), hip.stream())
             ap, npos, n_pred = ap_d.cpu().numpy(), npos_d.cpu().numpy(), n_pred_d.cpu().numpy()

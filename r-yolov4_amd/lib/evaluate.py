@@ -8,8 +8,6 @@ precision / recall curves; numpy's float64 expressions restated, bit-identical o
 host-side numpy restatement with the reference's signatures and return values, written independently (class-grouped, all IoU
 thresholds at once) — what the CPU tests pin to the fixture and the device path is compared with.
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -46,13 +44,11 @@ def get_batch_statistics(outputs, targets, iouv, niou):
         tgs = tg.to(dev)[order.to(dev)].contiguous() if ntgt else torch.zeros((0, 7), device=dev)
         iou_d = torch.as_tensor(iouv, dtype=torch.float32).to(dev).contiguous()
         tp = torch.empty((npred, niou), dtype=torch.uint8, device=dev)
-        need = ctypes.c_size_t()
-        hip.call("ryolo_map_match_workspace_bytes", npred, ntgt, need)
-        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        ws = hip.workspace("ryolo_map_match_workspace_bytes", npred, ntgt, device=dev)
         ncls = int(max(float(preds[:, 6].max()), float(tgs[:, 1].max()) if ntgt else 0.0)) + 1
         poff_d, toff_d = poff.to(dev), toff.to(dev)            # named: the device copies must outlive the launch
         hip.call("ryolo_map_match", hip.ptr(preds), hip.ptr(poff_d), hip.ptr(tgs) if ntgt else None, hip.ptr(toff_d), B, npred, ntgt,
-                 hip.ptr(iou_d), int(niou), ncls, hip.ptr(tp), hip.ptr(ws), need.value, hip.stream())
+                 hip.ptr(iou_d), int(niou), ncls, hip.ptr(tp), hip.ptr(ws), ws.numel(), hip.stream())
         # side effect of the reference: theta in degrees, in place, for images that have labels (and predictions)
         for b, o in enumerate(outputs):
             if len(o) and int(tcnt[b]):
@@ -148,9 +144,7 @@ def ap_per_class_device(tp, conf, pred_cls, target_cls, num_classes=None, device
         raise ValueError(f"ap_per_class_device: target class outside [0, {nc})")
     grid = torch.as_tensor(_RECALL_GRID).to(dev)
     cgrid = torch.as_tensor(_CONF_GRID).to(dev)
-    need = hip._Z()
-    hip.call("ryolo_ap_workspace_bytes", n, niou, nc, need)
-    ws = torch.empty(max(need.value, 16), dtype=torch.uint8, device=dev)
+    ws = hip.workspace("ryolo_ap_workspace_bytes", n, niou, nc, device=dev)
     ap = torch.empty((nc, niou), dtype=torch.float64, device=dev)
     prec_at = torch.empty((nc, _CONF_GRID.size), dtype=torch.float64, device=dev)
     rec_at = torch.empty_like(prec_at)

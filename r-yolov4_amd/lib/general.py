@@ -55,14 +55,12 @@ def _nms_sorted_batched(rboxes, counts, iou_thres, gt_only, max_keep):
     """rboxes [B,K,5] score-sorted; counts int32[B] or None.  Returns (keep int64[B,max_keep], num_keep int32[B])."""
     B, K = rboxes.shape[0], rboxes.shape[1]
     dev = rboxes.device
-    need = hip._Z()
-    hip.call("ryolo_nms_workspace_bytes", B, K, need)
-    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    ws = hip.workspace("ryolo_nms_workspace_bytes", B, K, device=dev)
     mk = K if max_keep is None else min(max_keep, K)
     keep = torch.empty((B, max(mk, 1)), dtype=torch.int64, device=dev)
     num = torch.empty(B, dtype=torch.int32, device=dev)
     hip.call("ryolo_nms_rotated_batched", hip.ptr(rboxes), hip.ptr(counts), B, K, float(iou_thres), 1 if gt_only else 0, mk,
-             hip.ptr(ws), need.value, hip.ptr(keep), keep.shape[1], hip.ptr(num), hip.stream())
+             hip.ptr(ws), ws.numel(), hip.ptr(keep), keep.shape[1], hip.ptr(num), hip.stream())
     return keep, num
 
 
@@ -74,10 +72,8 @@ def argsort_desc(scores):
     n = sc.shape[0]
     order = torch.empty(n, dtype=torch.int64, device=sc.device)
     if n:
-        need = hip._Z()
-        hip.call("ryolo_sort_workspace_bytes", 1, n, need)
-        ws = torch.empty(need.value, dtype=torch.uint8, device=sc.device)
-        hip.call("ryolo_argsort_desc", hip.ptr(sc), n, hip.ptr(order), hip.ptr(ws), need.value, hip.stream())
+        ws = hip.workspace("ryolo_sort_workspace_bytes", 1, n, device=sc.device)
+        hip.call("ryolo_argsort_desc", hip.ptr(sc), n, hip.ptr(order), hip.ptr(ws), ws.numel(), hip.stream())
     return order
 
 
@@ -89,10 +85,8 @@ def topk_desc(key, K):
     skey = torch.empty((B, K), dtype=torch.float32, device=key.device)
     order = torch.empty((B, K), dtype=torch.int64, device=key.device)
     if B and K:
-        need = hip._Z()
-        hip.call("ryolo_sort_workspace_bytes", B, K, need)
-        ws = torch.empty(need.value, dtype=torch.uint8, device=key.device)
-        hip.call("ryolo_topk_desc", hip.ptr(key), B, M, K, hip.ptr(skey), hip.ptr(order), None, hip.ptr(ws), need.value, hip.stream())
+        ws = hip.workspace("ryolo_sort_workspace_bytes", B, K, device=key.device)
+        hip.call("ryolo_topk_desc", hip.ptr(key), B, M, K, hip.ptr(skey), hip.ptr(order), None, hip.ptr(ws), ws.numel(), hip.stream())
     return skey, order
 
 
@@ -151,15 +145,12 @@ class PostProcessPlan:
         self.key = torch.empty((B, M), dtype=f32, device=device)
         self.cls = torch.empty((B, M), dtype=f32, device=device)
         self.count = torch.empty(B, dtype=i32, device=device)
-        need = hip._Z()
-        hip.call("ryolo_sort_workspace_bytes", B, K, need)
-        self.sort_ws = torch.empty(max(need.value, 16), dtype=torch.uint8, device=device)
+        self.sort_ws = hip.workspace("ryolo_sort_workspace_bytes", B, K, device=device)
         self.skey = torch.empty((B, K), dtype=f32, device=device)
         self.order = torch.empty((B, K), dtype=torch.int64, device=device)
         self.dets = torch.empty((B, K, 7), dtype=f32, device=device)
         self.rboxes = torch.empty((B, K, 5), dtype=f32, device=device)
-        hip.call("ryolo_nms_workspace_bytes", B, K, need)
-        self.nms_ws = torch.empty(max(need.value, 16), dtype=torch.uint8, device=device)
+        self.nms_ws = hip.workspace("ryolo_nms_workspace_bytes", B, K, device=device)
         self.mk = max(min(MAX_DET, K), 1)
         self.keep = torch.empty((B, self.mk), dtype=torch.int64, device=device)
         self.num = torch.empty(B, dtype=i32, device=device)

@@ -156,10 +156,9 @@ class _ComputeLossBase:
         items = torch.empty(6, dtype=torch.float32, device=dev)     # reg, conf, cls, theta, total, dropped target rows
         p = self._params(outs, targets, compute_grad, grads)
         self._last_shape, self._last_gs = (p.nt, self.na, p.batch), [o.shape[2] for o in outs]
-        need = S.Z()
-        hip.call("ryolo_loss_workspace_bytes", p, need)
-        if self._ws is None or self._ws.numel() < need.value or self._ws.device != dev:
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        need = hip.workspace_bytes("ryolo_loss_workspace_bytes", p)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
         p.ws, p.ws_bytes, p.items = self._ws.data_ptr(), self._ws.numel(), items.data_ptr()
         self._last_params = p
         if objgrad is not None:

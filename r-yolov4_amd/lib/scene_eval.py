@@ -99,10 +99,9 @@ class _Evaluator:
         return self._buf
 
     def _workspace(self, entry, *sizes):
-        need = hip._Z()
-        hip.call(entry, *sizes, need)
-        if self._ws is None or self._ws.numel() < need.value:
-            self._ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)     # the old one is released in stream order
+        need = hip.workspace_bytes(entry, *sizes)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)     # the old one is released in stream order
         return self._ws
 
     def _begin(self, out, num):

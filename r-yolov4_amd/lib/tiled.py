@@ -229,16 +229,14 @@ class ScenePlan:
         self.key = torch.empty((nc, ld), dtype=f32, device=dev)
         self.fkey = torch.empty(ld, dtype=f32, device=dev)
         self.Kc, self.Kf = min(det.max_nms, ld), min(det.max_det, ld)
-        need, need2 = hip._Z(), hip._Z()
-        hip.call("ryolo_sort_workspace_bytes", nc, self.Kc, need)
-        hip.call("ryolo_sort_workspace_bytes", 1, self.Kf, need2)
-        self.sort_ws = torch.empty(max(need.value, need2.value, 16), dtype=torch.uint8, device=dev)
+        # one sort workspace for both selections: the per-class one and the final one
+        sort_bytes = max(hip.workspace_bytes("ryolo_sort_workspace_bytes", nc, self.Kc), hip.workspace_bytes("ryolo_sort_workspace_bytes", 1, self.Kf))
+        self.sort_ws = torch.empty(max(sort_bytes, 16), dtype=torch.uint8, device=dev)
         self.skey = torch.empty((nc, self.Kc), dtype=f32, device=dev)
         self.order = torch.empty((nc, self.Kc), dtype=i64, device=dev)
         self.nsel = torch.empty(nc, dtype=i32, device=dev)
         self.rboxes = torch.empty((nc, self.Kc, 5), dtype=f32, device=dev)
-        hip.call("ryolo_nms_workspace_bytes", nc, self.Kc, need)
-        self.nms_ws = torch.empty(max(need.value, 16), dtype=torch.uint8, device=dev)
+        self.nms_ws = hip.workspace("ryolo_nms_workspace_bytes", nc, self.Kc, device=dev)
         self.keep = torch.empty((nc, self.Kc), dtype=i64, device=dev)
         self.nkeep = torch.empty(nc, dtype=i32, device=dev)
         self.fskey = torch.empty((1, self.Kf), dtype=f32, device=dev)
@@ -286,11 +284,10 @@ class ScenePlan:
         key, fkey = self.key, self.fkey
         if seam is not None:
             if self.flags is None:
-                dev, need = self.cand.device, hip._Z()
-                hip.call("ryolo_tile_seam_workspace_bytes", nc, Kc, need)
+                dev = self.cand.device
                 self.flags = torch.empty(self.ld, dtype=torch.uint8, device=dev)
                 self.seam_counts = torch.empty(2, dtype=torch.int32, device=dev)
-                self.seam_ws = torch.empty(max(need.value, 16), dtype=torch.uint8, device=dev)
+                self.seam_ws = hip.workspace("ryolo_tile_seam_workspace_bytes", nc, Kc, device=dev)
                 self.key2 = torch.empty((nc + 1, self.ld), dtype=torch.float32, device=dev)
             hip.call("ryolo_tile_seam_flags", hip.ptr(self.cand), hip.ptr(self.key), hip.ptr(self.win), hip.ptr(self.geom), self.T, self.nviews,
                      self.mk, self.ld, nc, self.size, seam.margin, 1 if seam.whole else 0, hip.ptr(self.flags),
