@@ -1,5 +1,5 @@
 // Device helpers and table records of the loader's pixel and label stages that more than one translation unit uses (augment.hip: whole
-// source images; scene.hip: windows of full-size scenes).  Moved here unchanged: both files compile the same arithmetic.
+// source images; scene.hip: windows of full-size scenes; copypaste.hip: pasted objects).  Moved here unchanged: the files compile the same arithmetic.
 #pragma once
 #include "common.h"
 
@@ -134,4 +134,16 @@ __device__ __forceinline__ AreaAxis area_axis(int d, int dn, int sn)
     a.has_hi = f2 - s2 > 1e-3;
     a.whi = (float)(fmin(fmin(f2 - s2, 1.0), cell) / cell);
     return a;
+}
+
+// twice the signed area of the polygon (x[k], y[k]), k < n (scene.hip: a label quad clipped to its window; copypaste.hip: a destination quad
+// and the part of a row that a pasted item covers)
+__device__ __forceinline__ double shoelace(const double* x, const double* y, int n)
+{
+    double s = 0.0;
+    for (int k = 0; k < n; k++) {
+        const int j = k + 1 == n ? 0 : k + 1;
+        s += x[k] * y[j] - x[j] * y[k];
+    }
+    return s;
 }

@@ -68,3 +68,13 @@ __device__ __forceinline__ double wave_sum_d(double v)
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+
+// exact n / d for 0 <= n < 2^16, 1 <= d < 2^16 with a float reciprocal (prologue index math; hipcc's generic 32-bit
+// division is ~40 instructions, the 64-bit one several hundred)
+__device__ __forceinline__ int small_div(int n, int d, float rd)
+{
+    int q = (int)((float)n * rd);
+    if (q * d > n) q--;
+    if ((q + 1) * d <= n) q++;
+    return q;
+}

@@ -651,6 +651,7 @@ __global__ __launch_bounds__(256, NST >= 5 ? 1 : 2) void conv_gemm_kernel(const 
                         const uint4 gz = *reinterpret_cast<const uint4*>(p.pool_dz + pp * p.pool_ld + n);
                         const unsigned want = (unsigned)((oh_ & 1) * 2 + (ow_ & 1));
                         const unsigned* a = reinterpret_cast<const unsigned*>(&v);
+                        // (restates pool_grad_merge, conv_internal.h: the call changes this kernel's schedule)
                         const unsigned* b = reinterpret_cast<const unsigned*>(&gz);
                         unsigned w[4];
 #pragma unroll
@@ -663,6 +664,7 @@ __global__ __launch_bounds__(256, NST >= 5 ? 1 : 2) void conv_gemm_kernel(const 
                     }
                     if (accum) {
                         const unsigned* a = reinterpret_cast<const unsigned*>(&v);
+                        // (restates accum_bf16x8, conv_internal.h: the call changes this kernel's schedule)
                         const unsigned* b = reinterpret_cast<const unsigned*>(&oldv[k]);
                         unsigned w[4];
 #pragma unroll
@@ -695,6 +697,7 @@ __global__ __launch_bounds__(256, NST >= 5 ? 1 : 2) void conv_gemm_kernel(const 
                     const uint4 gz = *reinterpret_cast<const uint4*>(p.pool_dz + pp * p.pool_ld + n);
                     const unsigned want = (unsigned)((oh_ & 1) * 2 + (ow_ & 1));
                     const unsigned* a = reinterpret_cast<const unsigned*>(&v);
+                    // (restates pool_grad_merge, conv_internal.h: the call changes this kernel's schedule)
                     const unsigned* b = reinterpret_cast<const unsigned*>(&gz);
                     unsigned w[4];
 #pragma unroll
@@ -712,6 +715,7 @@ __global__ __launch_bounds__(256, NST >= 5 ? 1 : 2) void conv_gemm_kernel(const 
                 if (p.epi == EPI_ACCUM) {
                     const uint4 old = *reinterpret_cast<const uint4*>(o);
                     const unsigned* a = reinterpret_cast<const unsigned*>(&v);
+                    // (restates accum_bf16x8, conv_internal.h: the call changes this kernel's schedule)
                     const unsigned* b = reinterpret_cast<const unsigned*>(&old);
                     unsigned w[4];
 #pragma unroll
@@ -735,12 +739,7 @@ __global__ __launch_bounds__(256, NST >= 5 ? 1 : 2) void conv_gemm_kernel(const 
 #pragma unroll
             for (int k = 0; k < WTM / RG; k++) {
                 const uint2 w = *reinterpret_cast<const uint2*>(stage + (rg + RG * k) * EP_LD + cq * 4);
-                const float f0 = __uint_as_float(w.x << 16), f1 = __uint_as_float(w.x & 0xffff0000u);
-                const float f2 = __uint_as_float(w.y << 16), f3 = __uint_as_float(w.y & 0xffff0000u);
-                ssum[0] += f0; ssq[0] += f0 * f0;
-                ssum[1] += f1; ssq[1] += f1 * f1;
-                ssum[2] += f2; ssq[2] += f2 * f2;
-                ssum[3] += f3; ssq[3] += f3 * f3;
+                stats_quad(w.x, w.y, ssum, ssq);
             }
             __syncthreads();                                   // staging blocks dead: LDS becomes the reduction buffer
             // every lane parks its 8 partial sums in LDS and one thread per column folds the RG x WM partials: the cross-lane

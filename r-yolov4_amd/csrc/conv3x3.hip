@@ -377,12 +377,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_patch_kernel(const ConvGemmPar
 #pragma unroll
             for (int k = 0; k < 16; k++) {
                 const uint2 w = *reinterpret_cast<const uint2*>(stage + (rg + 4 * k) * EP_LD + cq * 4);
-                const float f0 = __uint_as_float(w.x << 16), f1 = __uint_as_float(w.x & 0xffff0000u);
-                const float f2 = __uint_as_float(w.y << 16), f3 = __uint_as_float(w.y & 0xffff0000u);
-                ssum[0] += f0; ssq[0] += f0 * f0;
-                ssum[1] += f1; ssq[1] += f1 * f1;
-                ssum[2] += f2; ssq[2] += f2 * f2;
-                ssum[3] += f3; ssq[3] += f3 * f3;
+                stats_quad(w.x, w.y, ssum, ssq);
             }
         }
 #ifdef P3_TIMING
@@ -416,18 +411,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_patch_kernel(const ConvGemmPar
                 if (!lv[k]) continue;
                 const int r = (g0 + k) * RPI + r0;
                 uint4 v = *reinterpret_cast<const uint4*>(stage + r * EP_LD + ch * 8);
-                bf16_t* o = reinterpret_cast<bf16_t*>(p.out) + pixv[k] * p.ldC + ncol;
-                if (accum) {
-                    const unsigned* a = reinterpret_cast<const unsigned*>(&v);
-                    const unsigned* b = reinterpret_cast<const unsigned*>(&oldv[k]);
-                    unsigned w[4];
-#pragma unroll
-                    for (int q = 0; q < 4; q++)
-                        w[q] = pack_bf2(__uint_as_float(a[q] << 16) + __uint_as_float(b[q] << 16),
-                                        __uint_as_float(a[q] & 0xffff0000u) + __uint_as_float(b[q] & 0xffff0000u));
-                    v = make_uint4(w[0], w[1], w[2], w[3]);
-                }
-                *reinterpret_cast<uint4*>(o) = v;
+                const int64_t row = pixv[k] * p.ldC;
+                if (accum) accum_bf16x8(v, oldv[k]);
+                *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.out) + row + ncol) = v;
             }
         }
 #ifdef P3_TIMING

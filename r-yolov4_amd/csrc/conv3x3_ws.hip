@@ -182,26 +182,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         lv = (m < g.TH * g.TW) & col_ok;
         return reinterpret_cast<bf16_t*>(p.out) + ((int64_t)pix0 + (lv ? r * W + c : 0)) * p.ldC + (col_ok ? ncol : 0);
     };
-    auto stat_add = [&](const ry_u2& w) {
-        const float f0 = __uint_as_float(w.x << 16), f1 = __uint_as_float(w.x & 0xffff0000u);
-        const float f2 = __uint_as_float(w.y << 16), f3 = __uint_as_float(w.y & 0xffff0000u);
-        ssum[0] += f0; ssq[0] += f0 * f0;
-        ssum[1] += f1; ssq[1] += f1 * f1;
-        ssum[2] += f2; ssq[2] += f2 * f2;
-        ssum[3] += f3; ssq[3] += f3 * f3;
-    };
     auto store_seg = [&](bf16_t* o, bool lv, const ry_u4& sv, const uint4& old) {
         uint4 v = make_uint4(sv.x, sv.y, sv.z, sv.w);
-        if (ACCUM) {
-            const unsigned* a = reinterpret_cast<const unsigned*>(&v);
-            const unsigned* bb = reinterpret_cast<const unsigned*>(&old);
-            unsigned w[4];
-#pragma unroll
-            for (int e = 0; e < 4; e++)
-                w[e] = pack_bf2(__uint_as_float(a[e] << 16) + __uint_as_float(bb[e] << 16),
-                                __uint_as_float(a[e] & 0xffff0000u) + __uint_as_float(bb[e] & 0xffff0000u));
-            v = make_uint4(w[0], w[1], w[2], w[3]);
-        }
+        if (ACCUM) accum_bf16x8(v, old);
         if (lv) *reinterpret_cast<uint4*>(o) = v;
     };
 
@@ -257,7 +240,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             const bf16x8 cur = fr[u % PF];
             if constexpr (use_stats) {
 #pragma unroll
-                for (int q = 0; q < 4; q++) stat_add(sw[q]);
+                for (int q = 0; q < 4; q++) stats_quad(sw[q].x, sw[q].y, ssum, ssq);
             }
             if constexpr (use_store) {
                 constexpr int g0 = u == 33 + PF ? 0 : 4;
@@ -367,7 +350,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 for (int q = 0; q < 4; q++) w[q] = lds_rd64u(stg_addr8(rg + 8 * (k4 + q)));
                 lds_wait<0>(w[0], w[1], w[2], w[3]);
 #pragma unroll
-                for (int q = 0; q < 4; q++) stat_add(w[q]);
+                for (int q = 0; q < 4; q++) stats_quad(w[q].x, w[q].y, ssum, ssq);
             }
         }
 #pragma unroll

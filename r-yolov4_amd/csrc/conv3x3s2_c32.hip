@@ -148,12 +148,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_c32_kernel(const ConvGemmPar
             for (int k = 0; k < 8; k++) {
                 const int r = rg + 4 * k;
                 const uint2 w = *reinterpret_cast<const uint2*>(stage + r * 64 + (((cq >> 1) ^ (r & 7)) << 3) + (cq & 1) * 4);
-                const float f0 = __uint_as_float(w.x << 16), f1 = __uint_as_float(w.x & 0xffff0000u);
-                const float f2 = __uint_as_float(w.y << 16), f3 = __uint_as_float(w.y & 0xffff0000u);
-                ssum[0] += f0; ssq[0] += f0 * f0;
-                ssum[1] += f1; ssq[1] += f1 * f1;
-                ssum[2] += f2; ssq[2] += f2 * f2;
-                ssum[3] += f3; ssq[3] += f3 * f3;
+                stats_quad(w.x, w.y, ssum, ssq);
             }
         }
         // the staged reads are done before the next tile's writes land in the same tile (the wave's own LDS operations retire in order;

@@ -1,6 +1,7 @@
-// Pieces shared by the convolution translation units (conv.hip, conv3x3.hip): epilogue / activation codes, MFMA vector
-// types, the XCD-aware tile order.  Internal to libryolo_hip.so.
+// Pieces shared by the convolution translation units (conv.hip, conv3x3.hip, ...): epilogue codes and epilogue atoms, the activations (act.h),
+// MFMA vector types, the XCD-aware tile order.  Internal to libryolo_hip.so.
 #pragma once
+#include "act.h"
 #include "common.h"
 #include "params.h"
 #include <type_traits>
@@ -12,87 +13,42 @@ typedef __attribute__((address_space(1))) const void gbl_void_t;
 
 enum { EPI_RAW = 0, EPI_STATS = 1, EPI_AFFINE_ACT = 2, EPI_F32_BIAS = 3, EPI_ACCUM = 4,
        EPI_AFFINE_ACT_R = 5 };      // stem only: the conv output is rounded to bf16 BEFORE the affine map (= what the two-pass training path stores)
-enum { ACT_LINEAR = 0, ACT_MISH = 1, ACT_LEAKY = 2, ACT_SILU = 3 };
 
-__device__ __forceinline__ float act_fwd(float u, int act)
+// ---- epilogue atoms of the GEMM-shaped forward kernels: the router picks among those kernels by size, and a training result must not depend
+// on which one ran ---------------------------------------------------------------------------------------------------------------
+// BatchNorm batch statistics of the values actually stored: the 4 bf16 of two staged words, added to the lane's sums and sums of squares
+__device__ __forceinline__ void stats_quad(unsigned x, unsigned y, float (&ssum)[4], float (&ssq)[4])
 {
-    if (act == ACT_SILU) return u * __builtin_amdgcn_rcpf(1.f + __expf(-u));
-    if (act == ACT_LEAKY) return u > 0.f ? u : 0.1f * u;
-    if (act == ACT_MISH) {
-        if (u > 20.f) return u;
-        const float n = __expf(u), w = n * (n + 2.f);       // tanh(softplus(u)) = (n^2 + 2n) / (n^2 + 2n + 2)
-        return u * w * __builtin_amdgcn_rcpf(w + 2.f);
-    }
-    return u;
+    const float f0 = __uint_as_float(x << 16), f1 = __uint_as_float(x & 0xffff0000u);
+    const float f2 = __uint_as_float(y << 16), f3 = __uint_as_float(y & 0xffff0000u);
+    ssum[0] += f0; ssq[0] += f0 * f0;
+    ssum[1] += f1; ssq[1] += f1 * f1;
+    ssum[2] += f2; ssq[2] += f2 * f2;
+    ssum[3] += f3; ssq[3] += f3 * f3;
 }
-
-// Folded BatchNorm + activation of FOUR accumulator values (inference epilogues, EPI_AFFINE_ACT): v[q] = act(v[q] * sc[q] + sf[q]).  `act` is
-// wave-uniform; called per element through act_fwd every value paid the whole `if` chain (three scalar compare + branch pairs, and Mish's
-// `u > 20` early return as a DIVERGENT branch: 1 008 s_cbranch in the affine instantiation of the persistent pointwise kernel, r06 ISA count).  Here
-// the chain is walked once per quad and every arm is branch-free; the values are bit-identical to act_fwd's (same expressions, the Mish
-// cut-off as a select).
-template <int N> __device__ __forceinline__ void act_affine_vec(float (&v)[N], const float (&sc)[N], const float (&sf)[N], int act)
+// EPI_ACCUM store: v += old on 8 bf16, added in fp32 and rounded once
+__device__ __forceinline__ unsigned add_bf2(unsigned a, unsigned b)
 {
-    if (act == ACT_SILU) {
-#pragma unroll
-        for (int q = 0; q < N; q++) { const float u = v[q] * sc[q] + sf[q]; v[q] = u * __builtin_amdgcn_rcpf(1.f + __expf(-u)); }
-    } else if (act == ACT_MISH) {
-#pragma unroll
-        for (int q = 0; q < N; q++) {
-            const float u = v[q] * sc[q] + sf[q];
-            const float n = __expf(u), w = n * (n + 2.f);
-            const float r = u * w * __builtin_amdgcn_rcpf(w + 2.f);
-            v[q] = u > 20.f ? u : r;
-        }
-    } else if (act == ACT_LEAKY) {
-#pragma unroll
-        for (int q = 0; q < N; q++) { const float u = v[q] * sc[q] + sf[q]; v[q] = u > 0.f ? u : 0.1f * u; }
-    } else {
-#pragma unroll
-        for (int q = 0; q < N; q++) v[q] = v[q] * sc[q] + sf[q];
-    }
+    return pack_bf2(__uint_as_float(a << 16) + __uint_as_float(b << 16), __uint_as_float(a & 0xffff0000u) + __uint_as_float(b & 0xffff0000u));
 }
-__device__ __forceinline__ void act_affine_quad(float (&v)[4], const float (&sc)[4], const float (&sf)[4], int act) { act_affine_vec<4>(v, sc, sf, act); }
-
-// d act / du, same expressions as elementwise.hip's act_d (one v_exp_f32, v_rcp_f32 instead of IEEE division)
-__device__ __forceinline__ float act_bwd(float u, int act)
+__device__ __forceinline__ void accum_bf16x8(uint4& v, const uint4& old)
 {
-    if (act == ACT_SILU) { const float s = __builtin_amdgcn_rcpf(1.f + __expf(-u)); return s * (1.f + u * (1.f - s)); }
-    if (act == ACT_LEAKY) return u > 0.f ? 1.f : 0.1f;
-    if (act == ACT_MISH) {
-        if (u > 20.f) return 1.f;
-        const float n = __expf(u), w = n * (n + 2.f);
-        const float t = w * __builtin_amdgcn_rcpf(w + 2.f);
-        const float sg = n * __builtin_amdgcn_rcpf(1.f + n);
-        return t + u * (1.f - t * t) * sg;
-    }
-    return 1.f;
+    v = make_uint4(add_bf2(v.x, old.x), add_bf2(v.y, old.y), add_bf2(v.z, old.z), add_bf2(v.w, old.w));
 }
-
-// d act / du of N values with ONE walk of the (wave-uniform) activation chain and branch-free arms — bit-identical to N calls of act_bwd
-// (same expressions; Mish's `u > 20` cut-off as a select).  The fused first-layer backward (stem.hip) is instruction-rate bound: per element the
-// chain was three scalar compare + branch pairs plus a divergent early return.
-template <int N> __device__ __forceinline__ void act_bwd_vec(const float (&u)[N], float (&d)[N], int act)
+// MaxPool2d(2, 2) gradient merged into a data-gradient store: v += gz on the 8 channels whose recorded arg-max position (one byte per channel
+// in `packed`) is this pixel's position `want` inside its 2 x 2 window
+__device__ __forceinline__ void pool_grad_merge(uint4& v, const unsigned long long packed, const uint4& gz, const unsigned want)
 {
-    if (act == ACT_SILU) {
+    const unsigned* a = reinterpret_cast<const unsigned*>(&v);
+    const unsigned* b = reinterpret_cast<const unsigned*>(&gz);
+    unsigned w[4];
 #pragma unroll
-        for (int q = 0; q < N; q++) { const float s = __builtin_amdgcn_rcpf(1.f + __expf(-u[q])); d[q] = s * (1.f + u[q] * (1.f - s)); }
-    } else if (act == ACT_MISH) {
-#pragma unroll
-        for (int q = 0; q < N; q++) {
-            const float n = __expf(u[q]), w = n * (n + 2.f);
-            const float t = w * __builtin_amdgcn_rcpf(w + 2.f);
-            const float sg = n * __builtin_amdgcn_rcpf(1.f + n);
-            const float r = t + u[q] * (1.f - t * t) * sg;
-            d[q] = u[q] > 20.f ? 1.f : r;
-        }
-    } else if (act == ACT_LEAKY) {
-#pragma unroll
-        for (int q = 0; q < N; q++) d[q] = u[q] > 0.f ? 1.f : 0.1f;
-    } else {
-#pragma unroll
-        for (int q = 0; q < N; q++) d[q] = 1.f;
+    for (int q = 0; q < 4; q++) {
+        const float g0 = ((packed >> (16 * q)) & 0xff) == want ? __uint_as_float(b[q] << 16) : 0.f;
+        const float g1 = ((packed >> (16 * q + 8)) & 0xff) == want ? __uint_as_float(b[q] & 0xffff0000u) : 0.f;
+        w[q] = pack_bf2(__uint_as_float(a[q] << 16) + g0, __uint_as_float(a[q] & 0xffff0000u) + g1);
     }
+    v = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
 // ---- LDS transposed reads (ds_read_b64_tr_b16) next to LDS-DMA -----------------------------------------------------------------
@@ -209,16 +165,6 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg)
     const int q = nwg >> 3, r = nwg & 7;
     const int xcd = bid & 7, loc = bid >> 3;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-}
-
-// exact n / d for 0 <= n < 2^16, 1 <= d < 2^16 with a float reciprocal (prologue index math; hipcc's generic 32-bit
-// division is ~40 instructions, the 64-bit one several hundred)
-__device__ __forceinline__ int small_div(int n, int d, float rd)
-{
-    int q = (int)((float)n * rd);
-    if (q * d > n) q--;
-    if ((q + 1) * d <= n) q++;
-    return q;
 }
 
 // n / d == mulhi(n, m) >> s for 0 <= n < 2^31 (host side; kernels decompose pixel indices with it).  Division by one is flagged with m == 0.

@@ -22,16 +22,6 @@
 #define PASTE_TH 8
 #define PASTE_MAXV 20            // as SCENE_MAXV (scene.hip): the clip's vertex stores are bounded whatever the row's shape
 
-__device__ __forceinline__ double paste_shoelace(const double* x, const double* y, int n)
-{
-    double s = 0.0;
-    for (int k = 0; k < n; k++) {
-        const int j = k + 1 == n ? 0 : k + 1;
-        s += x[k] * y[j] - x[j] * y[k];
-    }
-    return s;
-}
-
 // s . ((bx - ax)(py - ay) - (by - ay)(px - ax)): >= 0 on the inner side of edge a -> b of a quad whose shoelace sum has sign s
 __device__ __forceinline__ double paste_edge(double ax, double ay, double bx, double by, double s, double px, double py)
 {
@@ -48,7 +38,7 @@ __device__ __forceinline__ bool paste_quad(const float* __restrict__ dq, int k, 
         qy[v] = (double)dq[(int64_t)k * 8 + 2 * v + 1];
         fin = fin && isfinite(qx[v]) && isfinite(qy[v]);
     }
-    const double s = paste_shoelace(qx, qy, 4);
+    const double s = shoelace(qx, qy, 4);
     sg = s > 0.0 ? 1.0 : -1.0;
     return fin && (s > 0.0 || s < 0.0);
 }
@@ -202,7 +192,7 @@ __global__ __launch_bounds__(256) void paste_labels_kernel(const float* __restri
     hi = min(hi, np);
     double ax[PASTE_MAXV], ay[PASTE_MAXV], bx[PASTE_MAXV], by[PASTE_MAXV];
     for (int k = 0; k < 4; k++) { ax[k] = (double)row[2 + 2 * k]; ay[k] = (double)row[3 + 2 * k]; }
-    const double area = fabs(paste_shoelace(ax, ay, 4));
+    const double area = fabs(shoelace(ax, ay, 4));
     bool occluded = false;
     if (area > 0.0) {                                               // (false for NaN coordinates too: the row stays as it is)
         for (int k = lo; k < hi && !occluded; k++) {
@@ -214,7 +204,7 @@ __global__ __launch_bounds__(256) void paste_labels_kernel(const float* __restri
             m = paste_clip_edge(bx, by, m, qx[1], qy[1], qx[2], qy[2], sg, ax, ay);
             m = paste_clip_edge(ax, ay, m, qx[2], qy[2], qx[3], qy[3], sg, bx, by);
             m = paste_clip_edge(bx, by, m, qx[3], qy[3], qx[0], qy[0], sg, ax, ay);
-            occluded = fabs(paste_shoelace(ax, ay, m)) / area >= occ_thr;
+            occluded = fabs(shoelace(ax, ay, m)) / area >= occ_thr;
         }
     }
 #pragma unroll

@@ -40,15 +40,8 @@ struct AnchorSet { float v[18 * 3]; };   // up to 18 anchors x (w, h, angle) in 
 // Every output element depends on ONE input element (its own column) and on the row's (anchor, grid cell): one LANE PER ELEMENT of the contiguous
 // [rows][attrs] array — coalesced 4-byte loads and stores (r05; the r01-r04 form gave a lane a whole 88-byte row: 22 strided scalar loads and 22
 // strided stores per lane, 0.6 TB/s, 10 % of the batch-64 inference forward).  A workgroup owns DK_EPW consecutive elements; its first row is
-// decomposed once (scalar 64-bit divisions), the rows inside by small exact divisions.
+// decomposed once (scalar 64-bit divisions), the rows inside by small exact divisions (small_div, common.h).
 #define DK_EPW 2048
-__device__ __forceinline__ int dk_div(int n, int d, float rd)
-{
-    int q = (int)((float)n * rd);
-    if (q * d > n) q--;
-    if ((q + 1) * d <= n) q++;
-    return q;
-}
 __global__ __launch_bounds__(256) void decode_kfiou_kernel(const float* __restrict__ t /*[B,na,gs,gs,attrs]*/, float* __restrict__ out, int B, int na,
                                                            int gs, int nc, float stride, AnchorSet an, int64_t row_offset, int64_t rows_per_image)
 {
@@ -71,21 +64,21 @@ __global__ __launch_bounds__(256) void decode_kfiou_kernel(const float* __restri
         const int64_t f = f0 + off;
         if (f >= total) break;
         const int local = k0 + off;                              // < DK_EPW + attrs
-        const int drow = dk_div(local, attrs, rattrs), k = local - drow * attrs;
+        const int drow = small_div(local, attrs, rattrs), k = local - drow * attrs;
         const float x = t[f];
         // (image, anchor, cell) of row0 + drow
         int cell = cell0 + drow;
-        const int da = dk_div(cell, cells, rcells);
+        const int da = small_div(cell, cells, rcells);
         cell -= da * cells;
         int a = a0 + da;
-        const int db = dk_div(a, na, rna);
+        const int db = small_div(a, na, rna);
         a -= db * na;
         const int b = b0 + db;
         const float s = sigmoid_acc(x);
         float v = s;                                            // columns >= 5: objectness and class scores
         if (k < 5) {
             if (k < 2) {
-                const int gy = dk_div(cell, gs, rgs), gx = cell - gy * gs;
+                const int gy = small_div(cell, gs, rgs), gx = cell - gy * gs;
                 v = (s * 2.f - 0.5f + (float)(k == 0 ? gx : gy)) * stride;
             } else if (k < 4) {
                 const float w2 = s * 2.f;

@@ -9,39 +9,9 @@
 // All activations are NHWC bf16 with a channel stride (`ld`) so outputs land directly in their torch.cat slice.
 // Every kernel moves 16 bytes (8 bf16) per lane per access; per-channel reductions are two-level and deterministic
 // (per-workgroup partial rows, then a finalize kernel accumulating in double) — no float atomics.
+#include "act.h"
 #include "common.h"
 #include "params.h"
-
-enum { ACT_LINEAR = 0, ACT_MISH = 1, ACT_LEAKY = 2, ACT_SILU = 3 };
-
-// Activations and their derivatives with ONE v_exp_f32 and one/two v_rcp_f32 per element (no IEEE division, no libm):
-// these kernels move 4-6 bytes per element, so a libm tanhf/log1pf or a correctly-rounded divide per element makes them
-// VALU-bound instead of HBM-bound.  Mish uses tanh(softplus(u)) = (n^2 + 2n) / (n^2 + 2n + 2) with n = e^u.
-__device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ float act_f(float u, int act)
-{
-    if (act == ACT_SILU) return u * fast_rcp(1.f + __expf(-u));
-    if (act == ACT_LEAKY) return u > 0.f ? u : 0.1f * u;
-    if (act == ACT_MISH) {
-        if (u > 20.f) return u;
-        const float n = __expf(u), w = n * (n + 2.f);
-        return u * w * fast_rcp(w + 2.f);
-    }
-    return u;
-}
-__device__ __forceinline__ float act_d(float u, int act)
-{
-    if (act == ACT_SILU) { const float s = fast_rcp(1.f + __expf(-u)); return s * (1.f + u * (1.f - s)); }
-    if (act == ACT_LEAKY) return u > 0.f ? 1.f : 0.1f;
-    if (act == ACT_MISH) {
-        if (u > 20.f) return 1.f;
-        const float n = __expf(u), w = n * (n + 2.f);
-        const float t = w * fast_rcp(w + 2.f);                 // tanh(softplus(u))
-        const float sg = n * fast_rcp(1.f + n);                // sigmoid(u)
-        return t + u * (1.f - t * t) * sg;
-    }
-    return 1.f;
-}
 
 struct V8 { float v[8]; };
 // Streaming access policy (same-box A/B on the whole step, yolov7 800^2 batch 64): these kernels touch every activation once or twice
@@ -259,7 +229,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const BnActParams p)
             for (int k = 0; k < 8; k++) {
                 float u = a.v[k] * sc1[k] + sh1[k];
                 if (Y2) u += b.v[k] * sc2[k] + sh2[k];
-                float zv = act_f(u, ACT);
+                float zv = act_fwd(u, ACT);
                 if (RES) zv += r.v[k];
                 o.v[k] = zv;
             }
@@ -316,7 +286,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_reduce_kernel(const BnActParam
                     for (int k = 0; k < 8; k++) {
                         float u = a.v[k] * sc1[k] + sh1[k];
                         if (Y2) u += b.v[k] * sc2[k] + sh2[k];
-                        const float g = d.v[k] * act_d(u, ACT);
+                        const float g = d.v[k] * act_bwd(u, ACT);
                         s0[k] += g;
                         s1[k] += g * a.v[k];
                         if (Y2) s2[k] += g * b.v[k];
@@ -459,7 +429,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(const BnActParams
             for (int k = 0; k < 8; k++) {
                 float u = a.v[k] * sc1[k] + sh1[k];
                 if (Y2) u += b.v[k] * sc2[k] + sh2[k];
-                const float g = d.v[k] * act_d(u, ACT);
+                const float g = d.v[k] * act_bwd(u, ACT);
                 o1.v[k] = sc1[k] * g + A1[k] * a.v[k] + B1[k];
                 if (Y2) o2.v[k] = sc2[k] * g + A2[k] * b.v[k] + B2[k];
             }

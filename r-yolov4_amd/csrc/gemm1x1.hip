@@ -195,18 +195,6 @@ __global__ __launch_bounds__(512, 1) void gemm1x1_ws_kernel(const ConvGemmParams
                     pool_want[q] = (a & 1) * 2 + (b & 1);
                 }
             }
-            auto pool_add = [&](uint4& v_, const unsigned long long packed, const uint4& gz, const unsigned want) {
-                const unsigned* a = reinterpret_cast<const unsigned*>(&v_);
-                const unsigned* b = reinterpret_cast<const unsigned*>(&gz);
-                unsigned w[4];
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    const float g0 = ((packed >> (16 * e)) & 0xff) == want ? __uint_as_float(b[e] << 16) : 0.f;
-                    const float g1 = ((packed >> (16 * e + 8)) & 0xff) == want ? __uint_as_float(b[e] & 0xffff0000u) : 0.f;
-                    w[e] = pack_bf2(__uint_as_float(a[e] << 16) + g0, __uint_as_float(a[e] & 0xffff0000u) + g1);
-                }
-                v_ = make_uint4(w[0], w[1], w[2], w[3]);
-            };
             const int rc = lane & 3, rr = lane >> 2;                // store phase: 16-byte chunk rc of rows rr + 16 it
             const int rsw = (rc ^ ((lane >> 3) & 3)) * 8;
             const int wsw = (l31 >> 1) & 3;
@@ -281,7 +269,7 @@ __global__ __launch_bounds__(512, 1) void gemm1x1_ws_kernel(const ConvGemmParams
                                 gz[it] = *reinterpret_cast<const uint4*>(p.pool_dz + pool_pp[it] * p.pool_ld + n);
                             }
 #pragma unroll
-                            for (int it = 0; it < 4; it++) pool_add(v[it], pk[it], gz[it], pool_want[it]);
+                            for (int it = 0; it < 4; it++) pool_grad_merge(v[it], pk[it], gz[it], pool_want[it]);
                         }
                         if constexpr (accum) {
                             uint4 oldv[4];
@@ -290,6 +278,7 @@ __global__ __launch_bounds__(512, 1) void gemm1x1_ws_kernel(const ConvGemmParams
 #pragma unroll
                             for (int it = 0; it < 4; it++) {
                                 const unsigned* a = reinterpret_cast<const unsigned*>(&v[it]);
+                                // (restates accum_bf16x8, conv_internal.h: the call changes this kernel's schedule)
                                 const unsigned* b = reinterpret_cast<const unsigned*>(&oldv[it]);
                                 unsigned w[4];
 #pragma unroll
@@ -308,11 +297,12 @@ __global__ __launch_bounds__(512, 1) void gemm1x1_ws_kernel(const ConvGemmParams
                         if (it * 16 + rr >= rows_left || !n_ok) continue;
                         uint4 w = v[it];
                         if constexpr (POOL)
-                            pool_add(w, *reinterpret_cast<const unsigned long long*>(p.pool_idx + pool_pp[it] * p.pool_ldi + n),
+                            pool_grad_merge(w, *reinterpret_cast<const unsigned long long*>(p.pool_idx + pool_pp[it] * p.pool_ldi + n),
                                      *reinterpret_cast<const uint4*>(p.pool_dz + pool_pp[it] * p.pool_ld + n), pool_want[it]);
                         if constexpr (accum) {
                             const uint4 old = *reinterpret_cast<const uint4*>(dst(it));
                             const unsigned* a = reinterpret_cast<const unsigned*>(&w);
+                            // (restates accum_bf16x8, conv_internal.h: the call changes this kernel's schedule)
                             const unsigned* b = reinterpret_cast<const unsigned*>(&old);
                             unsigned x[4];
 #pragma unroll
@@ -332,12 +322,7 @@ __global__ __launch_bounds__(512, 1) void gemm1x1_ws_kernel(const ConvGemmParams
 #pragma unroll
                     for (int k = 0; k < 8; k++) {
                         const uint2 w = *reinterpret_cast<const uint2*>(stage + (rg + 8 * k) * 32 + so);
-                        const float f0 = __uint_as_float(w.x << 16), f1 = __uint_as_float(w.x & 0xffff0000u);
-                        const float f2 = __uint_as_float(w.y << 16), f3 = __uint_as_float(w.y & 0xffff0000u);
-                        ssum[j][0] += f0; ssq[j][0] += f0 * f0;
-                        ssum[j][1] += f1; ssq[j][1] += f1 * f1;
-                        ssum[j][2] += f2; ssq[j][2] += f2 * f2;
-                        ssum[j][3] += f3; ssq[j][3] += f3 * f3;
+                        stats_quad(w.x, w.y, ssum[j], ssq[j]);
                     }
                 }
             }

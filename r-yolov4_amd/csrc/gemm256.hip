@@ -202,14 +202,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             }
             lds_wait<0>(w[0], w[1], w[2], w[3]);
 #pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const float f0 = __uint_as_float(w[q].x << 16), f1 = __uint_as_float(w[q].x & 0xffff0000u);
-                const float f2 = __uint_as_float(w[q].y << 16), f3 = __uint_as_float(w[q].y & 0xffff0000u);
-                ssum[0] += f0; ssq[0] += f0 * f0;
-                ssum[1] += f1; ssq[1] += f1 * f1;
-                ssum[2] += f2; ssq[2] += f2 * f2;
-                ssum[3] += f3; ssq[3] += f3 * f3;
-            }
+            for (int q = 0; q < 4; q++) stats_quad(w[q].x, w[q].y, ssum, ssq);
         }
     }
 #pragma unroll
@@ -231,16 +224,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             uint4 v = make_uint4(sv[q].x, sv[q].y, sv[q].z, sv[q].w);
-            if (ACCUM) {
-                const unsigned* a = reinterpret_cast<const unsigned*>(&v);
-                const unsigned* b = reinterpret_cast<const unsigned*>(&oldv[q]);
-                unsigned w[4];
-#pragma unroll
-                for (int e = 0; e < 4; e++)
-                    w[e] = pack_bf2(__uint_as_float(a[e] << 16) + __uint_as_float(b[e] << 16),
-                                    __uint_as_float(a[e] & 0xffff0000u) + __uint_as_float(b[e] & 0xffff0000u));
-                v = make_uint4(w[0], w[1], w[2], w[3]);
-            }
+            if (ACCUM) accum_bf16x8(v, oldv[q]);
             if (lv[q]) *reinterpret_cast<uint4*>(optr[q]) = v;
         }
     }

@@ -235,16 +235,6 @@ __device__ __forceinline__ int clip_plane(const double* ix, const double* iy, in
     return m;
 }
 
-__device__ __forceinline__ double shoelace(const double* x, const double* y, int n)
-{
-    double s = 0.0;
-    for (int k = 0; k < n; k++) {
-        const int j = k + 1 == n ? 0 : k + 1;
-        s += x[k] * y[j] - x[j] * y[k];
-    }
-    return s;
-}
-
 __global__ __launch_bounds__(256) void scene_label_rows_kernel(LabelRow* __restrict__ rows, int64_t n, const int* __restrict__ win_of_row,
                                                                const int* __restrict__ wins, int nwin, double thr, double* __restrict__ iof_out)
 {

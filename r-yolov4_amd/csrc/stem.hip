@@ -355,7 +355,7 @@ __global__ __launch_bounds__(256) void stem3x3_fwd_lds_kernel(const StemParams p
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfrag[0], f0, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfrag[1], f1, acc, 0, 0, 0);
         // r06: BatchNorm + activation of the tile's 16 values in ONE walk of the (wave-uniform) activation chain with branch-free arms
-        // (act_affine_vec, conv_internal.h): per element the chain cost three scalar compare + branch pairs in an instruction-rate-bound kernel
+        // (act_affine_vec, act.h): per element the chain cost three scalar compare + branch pairs in an instruction-rate-bound kernel
         float v16[16];
 #pragma unroll
         for (int e = 0; e < 16; e++) v16[e] = acc[e];
