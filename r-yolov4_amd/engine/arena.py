@@ -8,16 +8,14 @@ pass emits the same launches with arena addresses.  In training every forward ac
 the gradient twins: the gradients of the early (largest) layers are written at the end of backward, into the memory of the late layers'
 activations and gradients, dead by then.  In inference plans the activations themselves are recycled.
 
-Concurrency (Graph.run): a launch on a side stream may run later / earlier than its tape position, so its uses are widened to the
-interval of main-stream positions it can overlap with:
-  forward, lane 1 (a sibling branch)   [fork point of its branch, first main-stream launch after the next join)
-  forward, lane 2 (detection tails)    [fork point, end of the forward tape]
-  backward, weight gradient n          [its position, position of weight gradient n + LAG) — Graph.run makes the main stream wait for
-                                       weight gradient n before it enqueues number n + LAG (a bounded lag; without it every conv input
-                                       and every dY would have to stay until the end-of-tape join)
-Two buffers share memory only if their lifetimes are disjoint.  Serial replays (timing passes, CPU) are a special case of this order.
+Concurrency: a launch on a side stream may run later / earlier than its tape position, so each of its uses is widened to the interval of
+main-stream positions it can overlap with.  Which launch runs where and what waits for what is stated in engine/schedule.py, and the
+intervals are read off that statement (schedule.intervals) — this module holds no rule about streams.  Two buffers share memory only if
+their lifetimes are disjoint.  Serial replays (timing passes, CPU) are a special case of the scheduled order.
 """
 import ctypes as C
+
+from . import schedule
 
 VTAG = 1 << 60
 _IDSHIFT = 42
@@ -57,55 +55,30 @@ class Layout:
         self.off = {}            # buffer ident (2k: activation of Buf k, 2k + 1: its gradient) -> byte offset
         self.total = 0
         self.sum_bytes = 0
-        self.lag = 0
         self.names = None        # (forward, backward) kernel-name sequences of the dry pass: the second pass must repeat them
         self.life = {}           # ident -> (first, last) on the main stream's timeline (forward then backward positions)
 
 
-def lifetimes(g, lag):
-    F, B = len(g.fwd), len(g.bwd)
-    main_fwd = [i for i in range(F) if i not in g.fwd_side]
-    joins = sorted(g.fwd_join)
-
-    def fwd_interval(i):
-        ent = g.fwd_side.get(i)
-        if ent is None:
-            return i, i
-        f = i
-        while not g.fwd_side[f][0]:
-            f -= 1
-        if ent[1] == 2:
-            return f, F - 1
-        j = next((j for j in joins if j > i), F)
-        m = next((m for m in main_fwd if m >= j), F)          # where the main stream actually waits
-        return f, m - 1
-
-    side = sorted(g.side_idx)
-    pos = {t: n for n, t in enumerate(side)}
-
-    def bwd_interval(i):
-        n = pos.get(i)
-        if n is None:
-            return F + i, F + i
-        return F + i, F + (side[n + lag] - 1 if lag and n + lag < len(side) else B - 1)
-
-    life, pinned = {}, set()
-    for tape, ival in ((g.fwd, fwd_interval), (g.bwd, bwd_interval)):
-        tid = id(tape)
+def uses(g):
+    """g: a finished DRY Graph.  ident -> positions of the launches that mention the buffer, on ONE timeline: forward tape positions, then
+    len(g.fwd) + backward tape positions."""
+    out, base = {}, 0
+    for tape in (g.fwd, g.bwd):
         for i in range(len(tape)):
-            args = g._raw.get((tid, i))
-            if args is None:
-                continue
             ids = set()
-            for a in args:
+            for a in g._raw.get((id(tape), i), ()):
                 _tagged(a, ids)
-            if not ids:
-                continue
-            lo, hi = ival(i)
             for k in ids:
-                a = life.get(k)
-                life[k] = (lo, hi) if a is None else (min(a[0], lo), max(a[1], hi))
-    return life
+                out.setdefault(k, []).append(base + i)
+        base += len(tape)
+    return out
+
+
+def lifetimes(g):
+    """ident -> (first, last) on the main stream's timeline: the hull of the intervals its uses can overlap with under the tapes' schedules."""
+    F = len(g.fwd)
+    span = schedule.intervals(g.schedule(g.fwd), F) + [(F + lo, F + hi) for lo, hi in schedule.intervals(g.schedule(g.bwd), len(g.bwd))]
+    return {k: (min(span[p][0] for p in at), max(span[p][1] for p in at)) for k, at in uses(g).items()}
 
 
 def pack(sizes, life):
@@ -130,9 +103,9 @@ def pack(sizes, life):
     return off, total
 
 
-def plan(g, lag):
+def plan(g):
     """g: a finished DRY Graph.  Returns the Layout for the real pass."""
-    life = lifetimes(g, lag)
+    life = lifetimes(g)
     sizes = {}
     F, B = len(g.fwd), len(g.bwd)
     for ident, v in g._virt.items():
@@ -142,7 +115,6 @@ def plan(g, lag):
     lay = Layout()
     lay.off, lay.total = pack(sizes, life)
     lay.sum_bytes = sum((n + ALIGN - 1) // ALIGN * ALIGN for n in sizes.values())
-    lay.lag = lag
     lay.life = life
     lay.sizes = sizes
     lay.names = ([e[2] for e in g.fwd], [e[2] for e in g.bwd])

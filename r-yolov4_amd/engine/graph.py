@@ -19,6 +19,7 @@ import torch
 from .. import hip
 from . import arena
 from . import params as P
+from . import schedule
 from . import structs as S
 from .params import _classes_dgrad_s2, _fill_class, _taps_dgrad_s1, _taps_dgrad_s2d, _taps_fwd  # noqa: F401  (the engine's own tap tables)
 
@@ -111,13 +112,14 @@ class TRef:
 
 
 class Graph:
-    def __init__(self, rt, B, Hin, Win, training, frozen=False, dry=False, layout=None):
+    def __init__(self, rt, B, Hin, Win, training, frozen=False, dry=False, layout=None, lag=0):
         self.rt, self.B, self.Hin, self.Win, self.training = rt, B, Hin, Win, training
         # buffer placement (engine/arena.py): dry = liveness pass on virtual addresses; layout = its result, the buffers are slots of ONE arena
         self.dry, self.layout = dry, layout
         self._nbuf, self._virt, self._raw = 0, {}, {}
         self.arena = torch.empty(layout.total, dtype=torch.uint8, device=rt.device) if layout is not None else None
-        self._done = None                      # completion events of the weight-gradient launches (bounded lag, see run())
+        self.lag = lag                         # weight gradients the side streams may fall behind by (engine/schedule.py); 0 = unbounded
+        self._sched, self._bound = {}, {}      # per tape: its stream schedule, and the streams and events run() executes it with
         self.frozen = frozen                   # backward tape with eval-mode (running-statistics) BatchNorm
         self.batch_stats = training and not frozen
         self.dev = rt.device
@@ -128,8 +130,6 @@ class Graph:
         self.fwd_side = {}                     # forward-tape index -> True for the first entry of a forked branch, False for the rest
         self.fwd_join = set()                  # forward-tape indices before which the main stream joins the forked branch
         self.serial = False                    # True: everything on the main stream (per-kernel timing passes)
-        self._side = None                      # (stream, event pool)
-        self._side2 = None                     # (stream, join event) of forward lane 2
         self.stream = None
         self.img = torch.empty((B, 3, Hin, Win), dtype=torch.float32, device=self.adev)   # staging of the input batch
         self._img_slot, self._img_structs = None, []
@@ -296,123 +296,91 @@ class Graph:
                     last[k] = max(last[k], idx)
         return last
 
+    def schedule(self, tape):
+        """The stream schedule of a tape (engine/schedule.py), None for a tape that stays on the main stream.  Built once per plan; the
+        arena's liveness pass and run() both get it here, so both see the same lag."""
+        if tape is not self.fwd and tape is not self.bwd:
+            return None
+        if id(tape) not in self._sched:
+            self._sched[id(tape)] = (schedule.forward(len(tape), self.fwd_side, self.fwd_join) if tape is self.fwd else
+                                     schedule.backward(len(tape), self.side_idx, self.rt.wgrad_lanes, self.lag))
+        return self._sched[id(tape)]
+
+    def _bind(self, tape, sch):
+        """([stream of lane], [its raw handle], [event]) of a schedule.  The side STREAMS belong to the runtime (every plan of a model shares
+        them: a second plan with streams of its own pushed the process past its hardware queues and the 8-image plan ran 1.8x slower behind
+        the 64-image one); the events are the plan's own.  Slot 0 is the main stream: run() fills it in on every replay."""
+        b = self._bound.get(id(tape))
+        if b is None:
+            streams = [None] * (max(sch.stream) + 1)
+            for lane in sorted(set(sch.stream) - {0}):
+                streams[lane] = self.rt.side_stream(lane)
+            b = self._bound[id(tape)] = (streams, [s.cuda_stream if s is not None else None for s in streams],
+                                         [torch.cuda.Event() for _ in range(sch.events)])
+        return b
+
     def run(self, tape, timer=None, after=None):
         """Replay a tape.  after: {tape index: callable} invoked right after that launch was enqueued (gradient-bucket hooks).
 
-        Backward runs on TWO streams: the weight-gradient GEMMs (MFMA-bound, 22 ms of the step, results needed only by the optimizer)
-        go to a side stream behind an event, and overlap with the data-gradient / BatchNorm-backward chain of the earlier layers
-        (HBM-bound) that the main stream continues with.  The main stream joins the side stream before a gradient bucket is handed
-        to RCCL and at the end of the tape."""
+        On a GPU, unless `serial` is set, the tape runs on several streams: its schedule (engine/schedule.py) says which launch goes where
+        and which events are recorded and waited for around it; this loop only executes that.  Backward: the weight-gradient GEMMs
+        (MFMA-bound, 22 ms of the step, results needed only by the optimizer) overlap with the data-gradient / BatchNorm-backward chain of
+        the earlier layers (HBM-bound) that the main stream continues with."""
         st = hip.stream()
-        cuda = self.dev.type == "cuda" and not self.serial
-        side_idx = self.side_idx if (tape is self.bwd and self.side_idx and cuda) else None
-        fork = self.fwd_side if (tape is self.fwd and self.fwd_side and cuda) else None
-        if side_idx or fork:
-            if self._side is None:
-                n = max(len(self.fwd), len(self.bwd)) + 1
-                # the side STREAMS belong to the runtime (every plan of a model shares them: a second plan with streams of its own pushed
-                # the process past its hardware queues and the 8-image plan ran 1.8x slower behind the 64-image one); events per plan
-                self._side = (self.rt.side_stream(1), [torch.cuda.Event() for _ in range(2 * n)], torch.cuda.Event())
-            side, evs, join = self._side[:3]
-            n_ev = len(evs) // 2
-            main = torch.cuda.current_stream(self.dev)
-            sst = side.cuda_stream
-        lag = self.layout.lag if (side_idx is not None and self.layout is not None) else 0
-        if side_idx is not None:
-            if self._done is None:
-                order = sorted(self.side_idx)
-                self._done = ({t: n for n, t in enumerate(order)}, [torch.cuda.Event() for _ in order])
-            wpos, done = self._done
-            # weight gradient n runs on lane n % lanes: with small batches one weight-gradient kernel does not fill the GPU either
-            lanes = [side] + [self.rt.side_stream(2 + k) for k in range(1, max(1, self.rt.wgrad_lanes))]
-            if len(lanes) > 1 and len(self._side) == 3:
-                self._side = self._side + ([torch.cuda.Event() for _ in lanes],)
-            used = set()
+        sch = self.schedule(tape) if self.dev.type == "cuda" and not self.serial else None
+        if sch is not None:
+            streams, raw, events = self._bind(tape, sch)
+            streams[0] = torch.cuda.current_stream(self.dev)
+            lane_of, before, behind = sch.stream, sch.before, sch.after
+
+            def sync(ops):
+                for kind, e, s in ops:
+                    if kind == schedule.REC:
+                        events[e].record(streams[s])
+                    else:
+                        streams[s].wait_event(events[e])
         tid = id(tape)
-        dirty, dirty2, pending, lane_stream = False, False, None, None
-        probe = self.probe
+        skip_side = _DEBUG_SKIP_SIDE and tape is self.bwd
+        lane, lane_stream, probe = 0, None, self.probe
         for i, (fn, args, name) in enumerate(tape):
-            on_side = False
             pp = probe.get((tid, i)) if probe else None
             if pp is not None and pp[0] is not None:
                 pp[0]()                              # enqueued on the main stream BEFORE the fork event of a side-stream launch is recorded
-            if side_idx is not None:
-                on_side = i in side_idx
-                if on_side:                          # a weight gradient: its operands are final once everything before it ran
-                    if lag and wpos[i] >= lag:
-                        # bounded lag: weight gradient n - lag has finished before anything enqueued from here on starts — the arena
-                        # hands the memory of ITS operands to later launches on that promise (engine/arena.py)
-                        main.wait_event(done[wpos[i] - lag])
-                    evs[i].record(main)
-                    lane_stream = lanes[wpos[i] % len(lanes)]
-                    lane_stream.wait_event(evs[i])
-                    dirty = True
-                    used.add(wpos[i] % len(lanes))
-                    sst = lane_stream.cuda_stream
-            elif fork is not None:
-                if dirty and i in self.fwd_join:     # snapshot of the side stream at the join point (later forks are not waited for)
-                    pending = evs[n_ev + i]
-                    pending.record(side)
-                ent = fork.get(i)
-                on_side = ent is not None
-                if on_side:
-                    first, lane = ent
-                    if lane == 2:                    # long independent tails (detection heads): their own stream, joined at the end
-                        if self._side2 is None:
-                            self._side2 = (self.rt.side_stream(2), torch.cuda.Event())
-                        lane_stream = self._side2[0]
-                        dirty2 = True
-                    else:
-                        lane_stream = side
-                        dirty = True
-                    if first:                        # fork point of a branch: it may read everything enqueued so far
-                        evs[i].record(main)
-                        lane_stream.wait_event(evs[i])
-                    sst = lane_stream.cuda_stream
-                elif pending is not None:            # first main-stream launch after a join point
-                    main.wait_event(pending)
-                    pending = None
+            if sch is not None:
+                if before[i]:
+                    sync(before[i])
+                lane = lane_of[i]
+                lane_stream = streams[lane] if lane else None
             kind, fl, by, *sub = self.meta.get((tid, i), (name, 0, 0)) if timer is not None else (name, 0, 0)
-            if on_side and side_idx is not None and _DEBUG_SKIP_SIDE:
+            if lane and skip_side:
                 rc = 0                               # diagnostic only (RYOLO_DEBUG_SKIP_SIDE=1): the step WITHOUT its weight gradients = what the main stream costs alone
             elif fl:
                 e0, e1 = timer.pair()
-                e0.record(lane_stream if on_side else None)
-                rc = fn(*args, sst if on_side else st)
-                e1.record(lane_stream if on_side else None)
+                e0.record(lane_stream)
+                rc = fn(*args, raw[lane] if lane else st)
+                e1.record(lane_stream)
                 timer.note(kind, fl, e0, e1, by, *sub)
             else:
-                rc = fn(*args, sst if on_side else st)
+                rc = fn(*args, raw[lane] if lane else st)
             if rc != 0:
                 raise RuntimeError(f"{name} failed with code {rc}")
-            if lag and on_side:
-                done[wpos[i]].record(lane_stream)
+            if sch is not None and behind[i]:
+                sync(behind[i])
             if pp is not None and pp[1] is not None:
                 pp[1]()                              # (the callable synchronises the device itself when it reads a side-stream result)
             if after:
                 cb = after.get(i)
                 if cb is not None:
-                    if dirty:
-                        # the bucket may hold gradients written on the side stream: the hook's collective stream waits for this
-                        # event as well (parallel._Reducer._launch); the main stream is NOT stalled
-                        if side_idx is not None and len(lanes) > 1:      # all weight-gradient lanes funnel into lane 0 first
-                            for k in sorted(used - {0}):
-                                self._side[3][k].record(lanes[k])
-                                side.wait_event(self._side[3][k])
-                        join.record(side)
-                        self.rt.side_event = join
+                    if sch is not None:
+                        # the bucket may hold gradients written on a side stream: the hook's collective stream waits for this event
+                        # as well (parallel._Reducer._launch); the main stream is NOT stalled
+                        ops, ev = sch.hook[i]
+                        sync(ops)
+                        self.rt.side_event = events[ev] if ev is not None else None
                     cb()
                     self.rt.side_event = None
-        if dirty:
-            if side_idx is not None and len(lanes) > 1:
-                for k in sorted(used - {0}):
-                    self._side[3][k].record(lanes[k])
-                    main.wait_event(self._side[3][k])
-            join.record(side)
-            main.wait_event(join)
-        if dirty2:
-            self._side2[1].record(self._side2[0])
-            main.wait_event(self._side2[1])
+        if sch is not None:
+            sync(sch.end)
         self.rt.side_event = None
 
     # ------------------------------------------------------------------ convolution
@@ -473,7 +441,7 @@ class Graph:
                                         dW if dW is not None else self.rt.grad_ptr(conv.weight)), side=True)
 
     def _emit_wgrad(self, p, side=False):
-        """side: the launch may run on the weight-gradient stream (see run()): nothing on the main stream reads what it writes (the
+        """side: the launch may run on a weight-gradient stream (engine/schedule.py): nothing on the main stream reads what it writes (the
         split-K slabs and .grad) before the end of backward, and what it reads (a forward activation, the raw gradient of its own
         output) is final by the time it is enqueued."""
         p.zeros = self.rt.zeros.data_ptr()
@@ -481,8 +449,8 @@ class Graph:
         hip.call("ryolo_conv_wgrad_plan", p, sk, need)
         on_side = bool(side and self.rt.wgrad_stream)
         if on_side or not self.rt.wgrad_stream:
-            # launches of ONE stream are ordered, so they can share one split-K workspace; side launch n runs on lane n % lanes (run())
-            lane = len(self.side_idx) % max(1, self.rt.wgrad_lanes) if on_side else 0
+            # launches of ONE stream are ordered, so they can share one split-K workspace
+            lane = schedule.wgrad_lane(len(self.side_idx), self.rt.wgrad_lanes) if on_side else 0
             self._wgrad_ws_bytes[lane] = max(self._wgrad_ws_bytes.get(lane, 0), need.value)
             self._wgrads.setdefault(lane, []).append(p)
         else:

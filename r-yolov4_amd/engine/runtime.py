@@ -64,7 +64,7 @@ class Runtime:
         self._s2d = {}                    # id(conv) -> (conv, bf16 image [4 Cin][4][CoutP]) refreshed with the other packed weights
         self.side_event = None            # set by Graph.run around a gradient-bucket hook: event of the weight-gradient stream
         self.fwd_fork = os.environ.get("RYOLO_FWD_FORK", "1") != "0"              # sibling branches of ELAN / MaxConv blocks on two streams
-        self.wgrad_stream = os.environ.get("RYOLO_WGRAD_STREAM", "1") != "0"      # weight gradients on a second stream (Graph.run)
+        self.wgrad_stream = os.environ.get("RYOLO_WGRAD_STREAM", "1") != "0"      # weight gradients on a second stream (engine/schedule.py)
         # activations and their gradients of a plan as liveness-placed slots of one arena (engine/arena.py); 0 = one tensor per buffer
         self.buffer_reuse = os.environ.get("RYOLO_BUFFER_REUSE", "1") != "0"
         self.wgrad_lanes = int(os.environ.get("RYOLO_WGRAD_LANES", "1"))          # weight gradients round-robin over this many side streams
@@ -231,16 +231,19 @@ class Runtime:
             if not self.check_resident():
                 raise RuntimeError("ryolov4_amd: parameters were moved after the first forward; build a new Yolo/runtime")
             layout = None
+            # the bounded lag of the weight-gradient streams exists for the arena's sake: without reuse nothing waits for it.  Both planning
+            # passes get it, and each hands it to the schedule of its backward tape (Graph.schedule)
+            lag = self.wgrad_lag if self.buffer_reuse and self.wgrad_stream else 0
             if self.buffer_reuse:
                 # liveness pass on virtual addresses, then the real plan on one arena (engine/arena.py)
                 from . import arena
-                dry = Graph(self, B, H, W, training, frozen, dry=True)
+                dry = Graph(self, B, H, W, training, frozen, dry=True, lag=lag)
                 dry.begin()
                 self.model._emit(dry)
                 dry.finish()
-                layout = arena.plan(dry, self.wgrad_lag if self.wgrad_stream else 0)
+                layout = arena.plan(dry)
                 del dry
-            g = Graph(self, B, H, W, training, frozen, layout=layout)
+            g = Graph(self, B, H, W, training, frozen, layout=layout, lag=lag)
             g.begin()
             self.model._emit(g)
             g.finish()
