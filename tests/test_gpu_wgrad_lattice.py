@@ -7,8 +7,9 @@ that must reproduce the bits; dW2 / Cout1; channel strides wider than the tensor
 tables to the list of instantiations.  The randn tests of test_gpu_wgrad3x3.py / _taps.py / _wgrad1x1.py stay: fp32 rounding at workload sizes is
 their question, exactness at the boundaries is this file's.
 
-The first layer's direct kernel (`ryolo_stem3x3_wgrad`, plain form) is held to the same standard on an fp32 lattice image; its fused-activation
-form and `ryolo_stem3x3_bwd` evaluate an activation and are not exact on a lattice."""
+The first layer's direct kernel (`ryolo_stem3x3_wgrad`, plain form) is held to the same standard on an fp32 lattice image.  Its fused form
+(y != null) and `ryolo_stem3x3_bwd` evaluate an activation: with Mish / SiLU they are not exact on a lattice, with the linear activation
+(which every arm of act.h supports) they are, and tests/test_gpu_stem_lattice.py pins them bit for bit there."""
 import os
 import subprocess
 import sys

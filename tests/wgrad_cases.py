@@ -206,8 +206,21 @@ def operands(c, device="cpu", seed=None):
     return x, dy, dw0, ref, mag
 
 
-def mismatch_report(got, want, co0=0):
-    """Where a [rows, Cin, taps] gradient differs from the expected one: enough to point at a boundary without a second run."""
+def mismatch_report(got, want, co0=0, pixel_grid=None):
+    """Where a [rows, Cin, taps] gradient differs from the expected one: enough to point at a boundary without a second run.
+    With pixel_grid = (B, H, W) the tensors are [pixels, channels] outputs of a stride-1 layer instead (compared as given: pass bit
+    patterns to tell +0.0 from -0.0): first (pixel, channel), counts per image and per 32-pixel column block of the image rows."""
+    if pixel_grid is not None:
+        B, H, W = pixel_grid
+        bad = got != want
+        if got.is_floating_point():
+            bad = bad | torch.isnan(got)
+        p, ch = (int(v) for v in bad.nonzero()[0])
+        per_px = bad.view(B, H, W, -1).sum(3)
+        blocks = [int(per_px[:, :, 32 * b:32 * b + 32].sum()) for b in range((W + 31) // 32)]
+        return (f"{int(bad.sum())} of {bad.numel()} elements wrong; first (pixel, channel) = ({p}, {ch}) = image {p // (H * W)}, row {p // W % H}, column "
+                f"{p % W}: expected {want[p, ch].item()}, got {got[p, ch].item()}; wrong per image {per_px.sum((1, 2)).tolist()}; per 32-pixel column "
+                f"block {blocks}; per channel {bad.sum(0).tolist()}")
     bad = (got != want) | torch.isnan(got)
     n = int(bad.sum())
     idx = bad.nonzero()
