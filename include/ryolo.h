@@ -427,11 +427,32 @@ int ryolo_struct_sizes(int* sizes /* [11] */);
  * bbox_ciou (:36-78), KFLoss (:100-150).  Forward + gradient w.r.t. the head maps in one call; items[6] =
  * reg, conf, cls, theta, total (already scaled by the hyp gains), and the number of target rows whose image index lies outside
  * [0, batch) — the reference raises IndexError on those (lib/loss.py:209,385), this library skips them and reports the count.
+ *
+ * Ignore regions (LossParams.ignore / ni / ign_count; the reference has none — the rule is this build's, restated in numpy by
+ * tests/ignore_ref.py).  Row r = (image, x1, y1, x2, y2, x3, y3, x4, y4), coordinates normalised like targets[:, 2:6].  Per scale i:
+ *   v        = fl32(coordinate * (float)gs[i]), ONE fp32 multiply, then promoted to double: the GRID coordinates (X_k, Y_k), k = 0..3
+ *   S        = sum over k of (X_k * Y_k+1 - X_k+1 * Y_k) in vertex order, left to right, in double (the shoelace sum); s = +1 if S > 0 else -1
+ *   LIVE     image > -1.0f and image < (float)batch (for every finite value: 0 <= (int)image < batch; a NaN image is not live), all eight
+ *            coordinates finite, S != 0.  Any other row is DEAD: it covers nothing and is never an error, so a padded static table may end
+ *            in NaN rows.  b = (int)image.
+ *   centre   of cell (gj, gi): (cx, cy) = (gi + 0.5, gj + 0.5)
+ *   INSIDE   min X_k <= cx <= max X_k and min Y_k <= cy <= max Y_k (the bounding box the kernel walks; implied by the edge tests for a
+ *            convex quad), and for each of the four edges a -> b, a = vertex k, b = vertex k + 1:
+ *                s * ((bx - ax) * (cy - ay) - (by - ay) * (cx - ax)) >= 0
+ *            in double, each operation rounded on its own, no contraction (ryolo_paste_pixels' test).  Either vertex order works; a centre
+ *            on an edge is inside.
+ *   IGNORED  cell (b, a, gj, gi), for EVERY anchor a alike, iff no match owns it and its centre is inside some live row of image b.
+ * An ignored cell adds exactly 0 to the objectness sum; its objectness gradient is exactly 0.0f in grad[] and in objgrad[]; the rest of its
+ * grad[] row is zero as for any unmatched cell.  The objectness mean still divides by ALL cells of the scale: ignoring does not re-weight the
+ * other cells.  Matched cells are untouched (the owner's score stays their target even under a row), and so are the box, class and theta
+ * terms, the target assignment and the match records.  Works with compute_grad == 0 and with nt == 0.  Without rows the call issues the
+ * launches it issued before and every output is bit-identical.  ign_count (optional) is zeroed by the call and receives, per scale, the
+ * number of ignored cells.
  * ------------------------------------------------------------------------------------------------------------ */
 int ryolo_loss_workspace_bytes(const LossParams* p, size_t* bytes);
 int ryolo_loss(const LossParams* p, ryolo_stream_t stream);
-/* owner grids of the last ryolo_loss call with THESE params on this workspace: owner[i][cell] >= 0 iff cell of scale i was matched to a target (valid until
- * the next ryolo_loss on the workspace) */
+/* owner grids of the last ryolo_loss call with THESE params on this workspace: owner[i][cell] >= 0 iff cell of scale i was matched to a target; an
+ * unmatched cell holds -1, or -2 when the call ignored it (LossParams.ignore).  Readers test >= 0.  (Valid until the next ryolo_loss on the workspace) */
 int ryolo_loss_owner_grids(const LossParams* p, const int** owner);
 /* autograd chain rule of the loss node (lib/loss.py:256,414 return a [1] tensor; `loss.backward()` hands back d(out)/d(loss) as a
  * device scalar): grad[0..n) *= *scale, skipped ON THE DEVICE when *scale == 1.0f (the usual case) — no host read, capturable */

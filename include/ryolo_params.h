@@ -162,6 +162,9 @@ typedef struct LossParams {
     const float* headobj[3];  // optional: the objectness logit of every cell (head[i][cell * attrs + och]) as a compact [B, na, gs, gs] array, as
                               // ryolo_head_finish_fwd_obj leaves it; the objectness pass then reads 4 bytes per cell instead of one strided element
                               // of every row (= the whole map through the cache).  Must hold exactly the head maps' values.
+    const float* ignore; int ni;   // optional ignore regions (the rule: include/ryolo.h, ryolo_loss): [ni][9] = (image, x1, y1, ..., x4, y4), coordinates
+                              // normalised like targets[:, 2:6]; null / 0 = none (a zeroed block: the call is what it was before these fields existed)
+    int* ign_count;           // optional [3], device: unmatched cells of scale i that the call ignored (counted over b, a, gj, gi)
 } LossParams;
 
 /* ---- records of the device tables the data side uploads (datasets/augment.py); ryolo_*_bytes report their sizeof ---- */

@@ -17,6 +17,9 @@
 //                            order (what autograd's index_put_(accumulate=True) does, in a FIXED order) and stores them;
 //   K4 loss_obj_kernel       objectness BCE over every cell against the owner's IoU score (the only HBM-heavy pass: one logit per cell — from the
 //                            engine's compact copy, LossParams.headobj, else strided out of the map — and the definition of the gradient map);
+//   K3 loss_ignore_kernel    only with ignore rows (LossParams.ignore): a workgroup per (row, scale) walks the cells of the row's bounding box and
+//                            marks the unmatched ones whose centre the quad contains with -2 in the owner grid; K4 gives those cells value 0 and
+//                            gradient 0 (the rule: include/ryolo.h);
 //   K5 loss_finalize_kernel  fixed-order sums -> the five loss items, already scaled (lib/loss.py:251-255, :410-413).
 // Compiled with -ffp-contract=off so the float comparisons of target assignment match torch-CPU bit for bit.
 #include "common.h"
@@ -31,7 +34,7 @@ struct ScaleWs {
     int* count;               // [1]
     int* rec;                 // [cap][8]: b, a, gj, gi, cls, tidx, cell, pad
     float* frec;              // [cap][8]: tbox[0..4], score, pad, pad
-    int* owner;               // [cells]: largest match index of the cell (last writer wins), -1: no match
+    int* owner;               // [cells]: largest match index of the cell (last writer wins), -1: no match, -2: no match and ignored (loss_ignore_kernel)
     float* part_match;        // [nblk_match][4]: reg_a, reg_b, cls, theta
     float* part_obj;          // [nblk_obj]
     int* head;                // [cells]: most recently linked match of the cell (-1: none) — chains of duplicate matches
@@ -658,10 +661,73 @@ __global__ __launch_bounds__(256) void loss_match_grad_kernel(const LossParams p
         for (int q = 0; q < 3; q++) { const int k = lane + 64 * q; if (k < 180) gp[5 + p.nc + k] = gth[q]; }
 }
 
-// ------------------------------------------------------------------------------------------------ K3 / K4
+// ------------------------------------------------------------------------------------------------ K3 ignore rows
+// The rule of include/ryolo.h (ryolo_loss), restated by tests/ignore_ref.py.  Runs AFTER the match kernels: a cell that holds -1 then is unmatched
+// for good.  Rows that overlap only ever store the same value into a cell, so the grid does not depend on scheduling.  Edge test and shoelace sum as
+// copypaste.hip states them (paste_edge, shoelace of augment_px.h): double, one rounding per operation (this file is built with -ffp-contract=off).
+__global__ __launch_bounds__(256) void loss_ignore_kernel(const LossParams p, ScaleWs s0, ScaleWs s1, ScaleWs s2)
+{
+    const int scale = blockIdx.y;
+    const ScaleWs s = scale == 0 ? s0 : (scale == 1 ? s1 : s2);
+    const float* q = p.ignore + (int64_t)blockIdx.x * 9;
+    const float img = q[0];
+    if (!(img > -1.0f && img < (float)p.batch)) return;                              // (false for NaN; otherwise 0 <= (int)img < batch)
+    const int b = (int)img;
+    const int gs = p.gs[scale];
+    const float fg = (float)gs;
+    double qx[4], qy[4];
+    bool fin = true;
+#pragma unroll
+    for (int v = 0; v < 4; v++) {
+        const float cx = q[1 + 2 * v], cy = q[2 + 2 * v];
+        fin = fin && isfinite(cx) && isfinite(cy);
+        qx[v] = (double)(cx * fg);
+        qy[v] = (double)(cy * fg);
+    }
+    if (!fin) return;
+    double sh = 0.0;
+#pragma unroll
+    for (int v = 0; v < 4; v++) {
+        const int w = (v + 1) & 3;
+        sh += qx[v] * qy[w] - qx[w] * qy[v];
+    }
+    if (!(sh > 0.0 || sh < 0.0)) return;                                             // no area (or an overflow to inf - inf): covers nothing
+    const double sg = sh > 0.0 ? 1.0 : -1.0;
+    double x0 = qx[0], x1 = qx[0], y0 = qy[0], y1 = qy[0];
+#pragma unroll
+    for (int v = 1; v < 4; v++) {
+        x0 = fmin(x0, qx[v]); x1 = fmax(x1, qx[v]);
+        y0 = fmin(y0, qy[v]); y1 = fmax(y1, qy[v]);
+    }
+    // cells whose centre gi + 0.5 lies in [x0, x1], clipped to the grid; the clamp comes before the conversion to int
+    const double gd = (double)gs;
+    const int ix0 = (int)fmin(fmax(ceil(x0 - 0.5), 0.0), gd), ix1 = (int)fmin(fmax(floor(x1 - 0.5) + 1.0, 0.0), gd);
+    const int iy0 = (int)fmin(fmax(ceil(y0 - 0.5), 0.0), gd), iy1 = (int)fmin(fmax(floor(y1 - 0.5) + 1.0, 0.0), gd);
+    if (ix0 >= ix1 || iy0 >= iy1) return;
+    const int bw = ix1 - ix0, ncell = bw * (iy1 - iy0);
+    for (int t = threadIdx.x; t < ncell; t += 256) {
+        const int ty = t / bw;
+        const int gi = ix0 + (t - ty * bw), gj = iy0 + ty;
+        const double cx = (double)gi + 0.5, cy = (double)gj + 0.5;
+        bool in = cx >= x0 && cx <= x1 && cy >= y0 && cy <= y1;
+#pragma unroll
+        for (int v = 0; v < 4; v++) {
+            const int w = (v + 1) & 3;
+            in = in && sg * ((qx[w] - qx[v]) * (cy - qy[v]) - (qy[w] - qy[v]) * (cx - qx[v])) >= 0.0;
+        }
+        if (!in) continue;
+        for (int a = 0; a < p.na; a++) {
+            int* o = s.owner + ((b * p.na + a) * gs + gj) * gs + gi;                 // (b < batch, a < na, gj, gi < gs: inside [0, cells))
+            if (*o == -1) *o = -2;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ K4
 __global__ __launch_bounds__(256) void loss_obj_kernel(const LossParams p, ScaleWs s0, ScaleWs s1, ScaleWs s2)
 {
     __shared__ float red[4];
+    __shared__ int redi[4];
     const int scale = blockIdx.y;
     const ScaleWs s = scale == 0 ? s0 : (scale == 1 ? s1 : s2);
     if ((int)blockIdx.x >= s.nblk_obj) return;                                       // (one launch for the three scales: the grid is the largest one's)
@@ -671,6 +737,7 @@ __global__ __launch_bounds__(256) void loss_obj_kernel(const LossParams p, Scale
     const float rattrs = 1.0f / (float)attrs;
     const int lane = threadIdx.x & 63;
     float acc = 0.f;
+    int nign = 0;                                                                    // cells of this thread that an ignore row covers (owner == -2)
     // r05: this kernel also DEFINES the gradient map (it used to be cleared by a 1.3 GB hipMemsetAsync at the benchmark size, long before this pass
     // scattered one float per 88-byte row into it).  A wave owns 64 consecutive cells = one contiguous run of 64 * attrs floats: it writes the whole
     // run — zeros with the objectness gradient in place — as 16-byte stores; rows of MATCHED cells (owner >= 0) keep what loss_match_grad_kernel
@@ -685,9 +752,14 @@ __global__ __launch_bounds__(256) void loss_obj_kernel(const LossParams p, Scale
             const float x = p.headobj[scale] ? p.headobj[scale][i] : p.head[scale][(int64_t)i * attrs + och];
             own = s.owner[i];
             const float t = own >= 0 ? s.frec[(int64_t)own * 8 + 5] : 0.f;           // gr = 1.0: tconf = the owner's score (lib/loss.py:221), else 0
-            acc += fl_val(x, t, p.obj_pw, p.fl_gamma, p.fl_alpha);
+            // an ignored cell (own == -2, written by loss_ignore_kernel) adds exactly 0 and has gradient exactly 0; its row of the map is zero like
+            // any unmatched cell's (both store paths below test own >= 0 only)
+            const bool ign = own == -2;
+            nign += ign ? 1 : 0;
+            const float v = fl_val(x, t, p.obj_pw, p.fl_gamma, p.fl_alpha);
+            acc += ign ? 0.f : v;
             if (p.compute_grad) {
-                g = kg * fl_grad(x, t, p.obj_pw, p.fl_gamma, p.fl_alpha);
+                g = ign ? 0.f : kg * fl_grad(x, t, p.obj_pw, p.fl_gamma, p.fl_alpha);
                 if (p.objgrad[scale]) p.objgrad[scale][i] = g;
             }
         }
@@ -732,6 +804,14 @@ __global__ __launch_bounds__(256) void loss_obj_kernel(const LossParams p, Scale
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) s.part_obj[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+    if (p.ign_count) {                                                               // (uniform) one integer atomic per workgroup that ignored a cell
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) nign += __shfl_xor(nign, o, 64);
+        if ((threadIdx.x & 63) == 0) redi[threadIdx.x >> 6] = nign;
+        __syncthreads();
+        const int tot = redi[0] + redi[1] + redi[2] + redi[3];
+        if (threadIdx.x == 0 && tot > 0) atomicAdd(&p.ign_count[scale], tot);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ K5 finalize
@@ -817,6 +897,7 @@ extern "C" int ryolo_loss(const LossParams* pp, hipStream_t stream)
     if (p.na < 1 || p.na > LOSS_MAX_NA || p.nt < 0 || p.batch < 1 || p.nc < 0 || !p.items || !p.ws) return RY_ERR_ARG;
     if (p.nt > 0 && !p.targets) return RY_ERR_ARG;
     if (p.tcols < (p.mode == 0 ? 187 : 7) && p.nt > 0) return RY_ERR_ARG;
+    if (p.ni < 0) return RY_ERR_ARG;
     ScaleWs s[3];
     size_t need, ff_off, ff_bytes;
     carve(p, s, &need, &ff_off, &ff_bytes);
@@ -827,6 +908,7 @@ extern "C" int ryolo_loss(const LossParams* pp, hipStream_t stream)
     // gradient maps are defined by loss_match_grad_kernel + loss_obj_kernel
     if (hipMemsetAsync(p.ws, 0, 768, stream) != hipSuccess) return RY_ERR_LAUNCH;
     if (hipMemsetAsync(reinterpret_cast<char*>(p.ws) + ff_off, 0xff, p.compute_grad ? ff_bytes : ff_bytes / 2, stream) != hipSuccess) return RY_ERR_LAUNCH;
+    if (p.ign_count && hipMemsetAsync(p.ign_count, 0, 3 * sizeof(int), stream) != hipSuccess) return RY_ERR_LAUNCH;
     int max_obj = 1;
     for (int i = 0; i < 3; i++) max_obj = s[i].nblk_obj > max_obj ? s[i].nblk_obj : max_obj;
     if (p.nt > 0) {                                           // (one launch per pass for the three scales: blockIdx.y; cap is the same for all)
@@ -841,6 +923,8 @@ extern "C" int ryolo_loss(const LossParams* pp, hipStream_t stream)
         hipLaunchKernelGGL(loss_match_kernel, dim3((unsigned)ry_cdiv(s[0].cap, 256 / G), 3), dim3(256), 0, stream, p, s[0], s[1], s[2], G);
         if (p.compute_grad) hipLaunchKernelGGL(loss_match_grad_kernel, dim3(s[0].nblk_match, 3), dim3(256), 0, stream, p, s[0], s[1], s[2]);
     }
+    // ignore rows: after the match kernels (every owner is final), before the objectness pass that reads the marks
+    if (p.ignore && p.ni > 0) hipLaunchKernelGGL(loss_ignore_kernel, dim3((unsigned)p.ni, 3), dim3(256), 0, stream, p, s[0], s[1], s[2]);
     hipLaunchKernelGGL(loss_obj_kernel, dim3(max_obj, 3), dim3(256), 0, stream, p, s[0], s[1], s[2]);
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(1024), 0, stream, p, s[0], s[1], s[2]);
     RY_CHECK_LAUNCH();
@@ -848,6 +932,7 @@ extern "C" int ryolo_loss(const LossParams* pp, hipStream_t stream)
 }
 
 // the owner grids of the last ryolo_loss call on this workspace: owner[i][cell] >= 0 iff the cell of scale i was matched (its grad[] row is dense);
+// -1: unmatched, -2: unmatched and ignored (objectness gradient 0 like the rest of its row).  Readers test >= 0 (elementwise.hip);
 // valid until the next ryolo_loss on the same workspace
 extern "C" int ryolo_loss_owner_grids(const LossParams* pp, const int** owner)
 {

@@ -236,6 +236,12 @@ class BaseDataset:
         per batch; returns both (SceneDataset pastes objects here: datasets/copy_paste.py)."""
         return final, targets10
 
+    def _label_side_stage(self, uses, mats, flags):
+        """Called once per batch after ryolo_label_stage, with what the label rows were built from: uses [(resize-table row, slot, (h0, w0),
+        (h, w), Use, matrix index)] in row order, mats [n, 3, 3] float64 or None (the matrices the stage applied), flags uint8 [B] (the flip
+        decisions).  Does nothing here; a subclass that derives a second table from the same uses stages it with the same matrices
+        (SceneDataset: the ignore rows of a batch)."""
+
     # ------------------------------------------------------------------ the draws, in the reference's order
     def _load_image_plan(self, index, items, luts):
         """load_image (base_dataset.py:170-186) as a table row: resized size, interpolation, the hsv tables of this use.
@@ -352,7 +358,7 @@ class BaseDataset:
                 img = A.mixup(img, warped[id(canvases[b])], r)
             final[slot] = img
         # ---- labels: one table row per label of every source-image use, in the reference's concatenation order --------------------
-        rows, mats = [], []
+        rows, mats, uses = [], [], []
         for c in canvases:
             mat = -1
             if c["M"] is not None:
@@ -362,14 +368,17 @@ class BaseDataset:
                 for u, ds_index, hw0, hw in c["uses"]:
                     polys, cls = self._use_labels(ds_index, u.img)
                     rows.append(A.label_rows(polys, cls, c["slot"], hw0, hw, u, mat, self.normalized_labels))
+                    uses.append((u.img, c["slot"], hw0, hw, u, mat))
             else:
                 polys, cls = self._use_labels(c["index"], c["item"])
                 u = A.Use(c["item"], None, c["pad"], None, None)
                 rows.append(A.label_rows(polys, cls, c["slot"], c["hw0"], c["hw"], u, mat, self.normalized_labels))
+                uses.append((c["item"], c["slot"], c["hw0"], c["hw"], u, mat))
         rows = np.concatenate(rows) if rows else np.zeros(0, dtype=A.LABEL_ROW_DTYPE)
         # (mixup appends the second canvas' labels behind the first's: canvases of one sample are adjacent and in that order; samples are
         # in slot order, so the rows are already ordered the way collate_fn's torch.cat orders them)
         targets10 = A.label_stage_table(self._label_table(rows) if len(rows) else None, len(rows), np.stack(mats) if mats else None, dev)
+        self._label_side_stage(uses, np.stack(mats) if mats else None, flags)
         final, targets10 = self._canvas_stage(final, targets10, indices)
         imgs, targets = finalize_batch(final, targets10, A._to_device(flags, dev), self.csl)
         return [self.img_files[i] for i in indices], imgs, targets
@@ -451,6 +460,9 @@ class DeviceLoader:
         main.wait_event(done)
         imgs.record_stream(main)
         targets.record_stream(main)
+        ign = getattr(self.dataset, "last_ignore", None)         # (SceneDataset(ignore=...): the batch's ignore rows, consumed on `main` too)
+        if ign is not None:
+            ign.record_stream(main)
         return paths, imgs, targets
 
     def __iter__(self):

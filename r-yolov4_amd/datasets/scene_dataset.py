@@ -20,6 +20,7 @@ import os
 import random as _py_random
 
 import numpy as np
+import torch
 
 from . import augment as A
 from .base_dataset import BaseDataset
@@ -90,6 +91,49 @@ def cull_labels(polys, x0, y0, c, boxes=None):
     return np.nonzero((b[1] > x0) & (b[0] < x0 + c) & (b[3] > y0) & (b[2] < y0 + c))[0]
 
 
+class Ignore:
+    """Ignore regions of window training (SceneDataset(ignore=...)).  A label of which the window holds less than `iof_thr` of the area is
+    no target, yet its pixels are in the window; with this option every such label that keeps at least the share `iof_lo` becomes an IGNORE
+    ROW of the batch (`dataset.last_ignore`), under which the criterion's objectness term neither rewards nor punishes a prediction
+    (include/ryolo.h, ryolo_loss).  difficult=True: labels the DOTA / VOC protocol calls difficult are ignore rows too, and no targets —
+    what DotaEvaluator does with detections on them.  Off by default; the effect on DOTA mAP has not been measured."""
+    __slots__ = ("iof_lo", "difficult")
+
+    def __init__(self, iof_lo=0.1, difficult=True):
+        if isinstance(iof_lo, bool) or not isinstance(iof_lo, (int, float, np.integer, np.floating)) or not math.isfinite(iof_lo) or not 0 < iof_lo < 1:
+            raise ValueError(f"Ignore: iof_lo must be a number in (0, 1), below the dataset's iof_thr, got {iof_lo!r}")
+        if not isinstance(difficult, (bool, np.bool_)):
+            raise ValueError(f"Ignore: difficult must be a bool, got {difficult!r}")
+        self.iof_lo, self.difficult = float(iof_lo), bool(difficult)
+
+    def __repr__(self):
+        return f"Ignore(iof_lo={self.iof_lo}, difficult={self.difficult})"
+
+    def __eq__(self, other):
+        return isinstance(other, Ignore) and (self.iof_lo, self.difficult) == (other.iof_lo, other.difficult)
+
+    def __hash__(self):
+        return hash((self.iof_lo, self.difficult))
+
+
+def check_ignore(ignore, iof_thr):
+    """-> None or an Ignore, validated against the dataset's iof_thr (0 < iof_lo < iof_thr); a dict of Ignore's arguments is accepted."""
+    if ignore is None:
+        return None
+    if isinstance(ignore, dict):
+        try:
+            ignore = Ignore(**ignore)
+        except TypeError as e:
+            raise ValueError(f"ignore: {e}") from None
+    elif isinstance(ignore, Ignore):
+        ignore = Ignore(ignore.iof_lo, ignore.difficult)              # attributes set after construction are checked again
+    else:
+        raise ValueError(f"ignore must be None, an Ignore or a dict of its arguments, got {ignore!r}")
+    if not ignore.iof_lo < float(iof_thr):
+        raise ValueError(f"ignore: iof_lo must satisfy 0 < iof_lo < iof_thr = {iof_thr}, got {ignore.iof_lo}")
+    return ignore
+
+
 class SceneDataset(BaseDataset):
     """BaseDataset whose items are windows of scenes.  Subclasses fill `scene_files` / `scene_label_files`, implement `load_files` and call
     `plan_windows()`; `set_arrays(scenes, polys, labels)` does the same from decoded scenes.  `img_files` / `label_files` / `len()` are per
@@ -103,10 +147,21 @@ class SceneDataset(BaseDataset):
 
     copy_paste (a CopyPaste or a dict of its arguments; default None: off): with augment, labelled objects of the scenes the batch reads
     are pasted onto the finished canvases and their labels appended behind the batch's rows (datasets/copy_paste.py); `last_pastes`:
-    (slot, scene, label index, angle, scale, (cx, cy)) per pasted object of the last batch.  label_table() never pastes."""
+    (slot, scene, label index, angle, scale, (cx, cy)) per pasted object of the last batch.  label_table() never pastes.
+
+    ignore (an Ignore or a dict of its arguments; default None: off, not one launch more): per batch a SHADOW table of every label the host
+    cull hands to a use goes through ryolo_scene_label_rows with the threshold iof_lo and through ryolo_label_stage with the batch's own
+    matrices; a shadow row that is finite after the stage becomes an ignore row when its IoF is below iof_thr, or when `difficult` is on and
+    its label is difficult (those labels are then left out of the targets on the host).  `last_ignore`: float32 [ni, 9] on the device =
+    (slot, x1, y1, ..., x4, y4) with the flips of the slot applied and divided by the canvas side like the targets — the `ignore` argument
+    of the criterion; [0, 9] without rows, None when the option is off; valid until the next batch is requested.  Two extra launches, six
+    small uploads, a few element-wise torch operations and one host read (the row count) per batch.  The windows, every draw from `rng`,
+    copy-paste (pastes neither bury ignore rows nor count them for occ_thr), keep_empty and label_table() are what they are without it.
+    Not covered: rows that the centre filter of ryolo_encode_labels drops on the plain DOTADataset path, and ignore rows of a mixup
+    partner beyond carrying its slot."""
 
     def __init__(self, hyp, img_size, augment, csl, normalized_labels=False, overlap=200, rates=(1.0,), iof_thr=0.7, keep_empty=False,
-                 jitter=None, p_object=0.5, window_seed=0, copy_paste=None, **device_kw):
+                 jitter=None, p_object=0.5, window_seed=0, copy_paste=None, ignore=None, **device_kw):
         super().__init__(hyp, img_size, augment, csl, normalized_labels, **device_kw)
         if normalized_labels:
             raise ValueError("SceneDataset: scene labels are in scene pixels (normalized_labels=False)")
@@ -115,6 +170,9 @@ class SceneDataset(BaseDataset):
         if not (0.0 <= float(p_object) <= 1.0):
             raise ValueError(f"SceneDataset: p_object is a probability, got {p_object}")
         scene_windows(1, 1, img_size, overlap, rates)               # argument errors now, not at the first scene
+        self.ignore = check_ignore(ignore, iof_thr)
+        self.last_ignore = self._ignore_pending = None
+        self._shadow = {}                                          # resize-table row -> (polys, classes, difficult flags) the cull handed to that use
         self.overlap, self.rates, self.iof_thr, self.keep_empty = overlap, tuple(rates), float(iof_thr), bool(keep_empty)
         self.jitter = bool(augment) if jitter is None else bool(jitter)
         self.p_object = float(p_object)
@@ -158,12 +216,16 @@ class SceneDataset(BaseDataset):
     def _parse_difficult(self, scene):
         return None
 
-    def _window_labels(self, scene, x0, y0, c):
-        polys, cls = self.scene_labels(scene)
+    def _window_cull(self, scene, x0, y0, c):
+        polys, _ = self.scene_labels(scene)
         boxes = self._boxes.get(scene)
         if boxes is None:
             boxes = self._boxes[scene] = label_boxes(polys)
-        keep = cull_labels(polys, x0, y0, c, boxes)
+        return cull_labels(polys, x0, y0, c, boxes)
+
+    def _window_labels(self, scene, x0, y0, c):
+        polys, cls = self.scene_labels(scene)
+        keep = self._window_cull(scene, x0, y0, c)
         return polys[keep], cls[keep]
 
     def plan_windows(self):
@@ -237,7 +299,16 @@ class SceneDataset(BaseDataset):
 
     def _use_labels(self, index, row):
         _, s, x0, y0, c = self.last_windows[row]
-        polys, cls = self._window_labels(s, x0, y0, c)
+        if self.ignore is None:
+            polys, cls = self._window_labels(s, x0, y0, c)
+        else:
+            # the shadow of this use: everything the cull kept, difficult labels included; with Ignore.difficult those are no targets
+            keep = self._window_cull(s, x0, y0, c)
+            polys, cls = (v[keep] for v in self.scene_labels(s))
+            diff = self.scene_difficult(s)[keep]
+            self._shadow[row] = (polys, cls, diff)
+            if self.ignore.difficult:
+                polys, cls = polys[diff == 0], cls[diff == 0]
         self._row_wins.append(np.full(len(cls), row, dtype=np.int32))
         return polys, cls
 
@@ -252,8 +323,50 @@ class SceneDataset(BaseDataset):
         return table
 
     def assemble_batch(self, indices):
-        self.last_windows, self._row_wins = [], []
-        return super().assemble_batch(indices)
+        self.last_windows, self._row_wins, self._shadow = [], [], {}
+        self.last_ignore = self._ignore_pending = None
+        batch = super().assemble_batch(indices)
+        if self._ignore_pending is not None:
+            # the rows were chosen on the device in _label_side_stage; the compaction needs their count on the host, and here — behind
+            # finalize_batch's own read — that wait is over work that has already finished
+            out, sel = self._ignore_pending
+            self.last_ignore, self._ignore_pending = out[sel], None
+        return batch
+
+    def _label_side_stage(self, uses, mats, flags):
+        """The ignore rows of the batch (class docstring; restated by tests/ignore_ref.py): the shadow table through the window test at iof_lo
+        and the stage with the batch's matrices, the choice of rows, then the coordinate maps ryolo_encode_labels applies to labels — the
+        division by the canvas side and the flips of the slot, the same fp32 operations."""
+        ig = self.ignore
+        if ig is None:
+            return
+        dev, S = self.device, self.img_size
+        rows, wins, hard = [], [], []
+        for row, slot, hw0, hw, u, mat in uses:
+            polys, cls, diff = self._shadow[row]
+            rows.append(A.label_rows(polys, cls, slot, hw0, hw, u, mat, self.normalized_labels))
+            wins.append(np.full(len(cls), row, dtype=np.int32))
+            hard.append(diff)
+        rows = np.concatenate(rows) if rows else np.zeros(0, dtype=A.LABEL_ROW_DTYPE)
+        n = len(rows)
+        if not n:
+            self.last_ignore = torch.empty((0, 9), dtype=torch.float32, device=dev)
+            return
+        table = A.upload_label_rows(rows, dev)
+        iof = A.scene_label_rows(table, n, np.concatenate(wins), [w[2:] for w in self.last_windows], ig.iof_lo, want_iof=True)
+        t10 = A.label_stage_table(table, n, mats, dev)              # (slot, class, 8 vertices in canvas pixels; NaN: below iof_lo or filtered)
+        quad = t10[:, 2:10]
+        sel = iof < self.iof_thr
+        if ig.difficult:
+            sel = sel | (A._to_device(np.concatenate(hard).astype(np.uint8), dev) != 0)
+        sel = sel & torch.isfinite(quad).all(dim=1)
+        f = A._to_device(np.asarray(flags, dtype=np.uint8), dev)[t10[:, 0].long()]
+        x, y = quad[:, 0::2] / float(S), quad[:, 1::2] / float(S)
+        x = torch.where((f & 1).bool()[:, None], 1.0 - x, x)
+        y = torch.where((f & 2).bool()[:, None], 1.0 - y, y)
+        out = torch.empty((n, 9), dtype=torch.float32, device=dev)
+        out[:, 0], out[:, 1::2], out[:, 2::2] = t10[:, 0], x, y
+        self._ignore_pending = (out, sel)                            # (compacted at the end of assemble_batch)
 
     # ------------------------------------------------------------------ copy-paste on the finished canvases
     def class_counts(self):
@@ -295,12 +408,12 @@ class SceneDataset(BaseDataset):
     def _label_chunk(self, indices):
         """BaseDataset._label_chunk over the PLANNED windows: jitter is off for its duration (the window generator is not touched) and the
         window tables of the last batch are put back afterwards."""
-        saved = self.jitter, self.last_windows, self._row_wins
-        self.jitter, self.last_windows, self._row_wins = False, [], []
+        saved = self.jitter, self.last_windows, self._row_wins, self.ignore
+        self.jitter, self.last_windows, self._row_wins, self.ignore = False, [], [], None       # (the table holds every target: no ignore rows here)
         try:
             return super()._label_chunk(indices)
         finally:
-            self.jitter, self.last_windows, self._row_wins = saved
+            self.jitter, self.last_windows, self._row_wins, self.ignore = saved
 
 
 class DOTASceneDataset(SceneDataset):

@@ -5,6 +5,8 @@ with zero targets.  One device->host read per call (the reference does 4-5); pas
 (loss_items then holds 0-d device tensors) — the training benchmark uses this.
 FocalLoss (lib/loss.py:10-33; inactive in the reference's configuration, fl_gamma: 0.0, data/hyp.yaml:12) wraps every BCE term
 inside the same kernels when hyp['fl_gamma'] > 0.
+Ignore regions (this build's extra, off unless asked for): `__call__(outputs, target, ignore=rows)` with rows [ni, 9] = (image, four
+vertices) — unmatched cells under a quad of their image add neither loss nor gradient to objectness (include/ryolo.h, ryolo_loss).
 """
 import os
 
@@ -63,8 +65,8 @@ def clear_handoff():
 
 class _LossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, owner, targets, o0, o1, o2):
-        grads, items = owner._run([o0, o1, o2], targets, True)
+    def forward(ctx, owner, targets, ignore, o0, o1, o2):
+        grads, items = owner._run([o0, o1, o2], targets, True, ignore)
         ctx.grads = grads
         ctx.crit, ctx.gen, ctx.compact = owner, owner._gen, owner._compact
         ctx.consumed = False
@@ -94,7 +96,7 @@ class _LossFn(torch.autograd.Function):
         for k, t in enumerate(arrs):
             ptrs[k], lens[k] = t.data_ptr(), t.numel()
         hip.call("ryolo_loss_grad_scale_multi", ptrs, lens, len(arrs), sc.data_ptr(), hip.stream())       # one launch (exits on the device when the scalar is 1)
-        return (None, None) + tuple(g)
+        return (None, None, None) + tuple(g)
 
 
 class _ComputeLossBase:
@@ -117,6 +119,8 @@ class _ComputeLossBase:
         self._drop_batch = 0
         self._gen = 0
         self._compact = None
+        self.ignored_cells = None                   # int32 [3] on the device after a call: cells of each scale the call ignored
+        self._no_ignored = None
 
     def _params(self, outputs, targets, compute_grad, grads):
         p = S.LossParams()
@@ -138,9 +142,20 @@ class _ComputeLossBase:
         p.fl_gamma, p.fl_alpha = self.fl_gamma, 0.25             # FocalLoss(loss_fcn, gamma) keeps its default alpha (lib/loss.py:11)
         return p
 
-    def _run(self, outputs, targets, compute_grad):
+    @staticmethod
+    def _ignore_rows(ignore, dev):
+        """The `ignore` argument of a call as a contiguous float32 [ni, 9] device tensor (None: no rows); any other shape raises."""
+        if ignore is None:
+            return None
+        if not isinstance(ignore, torch.Tensor) or ignore.dim() != 2 or ignore.shape[1] != 9 or not ignore.is_floating_point():
+            raise RuntimeError("loss: ignore must be a float tensor [ni, 9] = (image, x1, y1, ..., x4, y4), got {}".format(
+                tuple(ignore.shape) if isinstance(ignore, torch.Tensor) else type(ignore).__name__))
+        return ignore.detach().to(dev).float().contiguous()
+
+    def _run(self, outputs, targets, compute_grad, ignore=None):
         S.check_layouts()
         dev = outputs[0].device
+        ignore = self._ignore_rows(ignore, dev)                       # (a bad shape raises here: before any launch)
         attrs = self.nc + (185 if self.MODE == 0 else 6)              # (MODEs 2-5 share the kfiou head layout)
         outs = []
         for o in outputs:
@@ -168,6 +183,15 @@ class _ComputeLossBase:
         for i in range(3):
             p.headobj[i] = xobj[i].data_ptr() if xobj[i] is not None else None
         self._used_head_obj = [x is not None for x in xobj]
+        if ignore is not None and ignore.shape[0]:
+            # ignore rows: the objectness pass skips the unmatched cells under them (include/ryolo.h, ryolo_loss) and counts them per scale
+            self.ignored_cells = torch.empty(3, dtype=torch.int32, device=dev)     # (zeroed by the call)
+            p.ignore, p.ni, p.ign_count = ignore.data_ptr(), ignore.shape[0], self.ignored_cells.data_ptr()
+        else:
+            # no rows: the fields stay zero and the call is, launch for launch, what it was; the count is one zeros tensor per device, made once
+            if self._no_ignored is None or self._no_ignored.device != dev:
+                self._no_ignored = torch.zeros(3, dtype=torch.int32, device=dev)
+            self.ignored_cells = self._no_ignored
         hip.call("ryolo_loss", p, hip.stream())
         if objgrad is not None:
             own = (S.P * 3)()
@@ -206,13 +230,16 @@ class _ComputeLossBase:
             out.append(ws[o:o + cnt * 32].view(torch.int32).reshape(-1, 8).cpu().numpy().astype("int64"))
         return out
 
-    def __call__(self, outputs, target, sync_items=True):
+    def __call__(self, outputs, target, ignore=None, sync_items=True):
+        """ignore (optional): float tensor [ni, 9] = (image, x1, y1, ..., x4, y4), quads normalised like the targets (SceneDataset.last_ignore):
+        unmatched cells whose centre lies in a quad of their image contribute neither loss nor gradient to objectness.  `ignored_cells`
+        (int32 [3], device; never read here) then holds the number of such cells per scale — zeros without rows."""
         needs_grad = torch.is_grad_enabled() and any(o.requires_grad for o in outputs)
         if needs_grad:
-            loss = _LossFn.apply(self, target, *outputs)
+            loss = _LossFn.apply(self, target, ignore, *outputs)
             items = self._last_items
         else:
-            _, items = self._run(list(outputs), target, False)
+            _, items = self._run(list(outputs), target, False, ignore)
             loss = items[4:5].clone()
         names = ("reg_loss", "conf_loss", "cls_loss", "theta_loss", "total_loss")
         self.dropped_targets = items[5]                # device scalar: rows whose image index is outside [0, batch)

@@ -4,11 +4,18 @@ calls after `--warmup`, the whole round repeated `--runs` times with the losses 
 runs can be read next to the differences between losses.  Prints one JSON line.
 
     python tools/bench_loss.py [--losses kfiou,kld,gwd,probiou] [--batch 64] [--size 800] [--iters 50] [--warmup 10] [--runs 2]
+                               [--ignore-rows 0,2048]
 
-RYOLO_LIB=<another build of libryolo_hip.so> times that build instead (A/B against another commit)."""
+--ignore-rows: every loss is also timed with that many ignore rows per batch (`criterion(..., ignore=table)`; 0 = the plain call): random
+rotated boxes of 16 .. 128 pixels spread over the images, so the marking kernel walks bounding boxes of the size real labels have.  A
+case with rows is reported as "<loss>+<n>rows".
+
+RYOLO_LIB=<another build of libryolo_hip.so> times that build instead (A/B against another commit with the SAME struct layouts; a commit
+from before a parameter block grew is timed from its own checkout with this tool's version there)."""
 import argparse
 import json
 import os
+import math
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,6 +29,21 @@ class _Model:
     pass
 
 
+def ignore_table(n, batch, size, dev, seed=7):
+    """n ignore rows [n, 9] = (image, four vertices normalised): rotated boxes with sides of 16 .. 128 pixels, centres anywhere."""
+    g = torch.Generator().manual_seed(seed)
+    u = torch.rand(n, 6, generator=g)
+    img = torch.floor(u[:, 0] * batch)
+    cx, cy = u[:, 1] * size, u[:, 2] * size
+    w, h = 16.0 * 8.0 ** u[:, 3], 16.0 * 8.0 ** u[:, 4]
+    th = (u[:, 5] - 0.5) * math.pi
+    c, s_ = torch.cos(th), torch.sin(th)
+    out = [img]
+    for sx, sy in ((-0.5, -0.5), (0.5, -0.5), (0.5, 0.5), (-0.5, 0.5)):
+        out += [(cx + sx * w * c - sy * h * s_) / size, (cy + sx * w * s_ + sy * h * c) / size]
+    return torch.stack(out, 1).float().to(dev)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--losses", default="kfiou,kld,gwd,probiou")
@@ -31,6 +53,7 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--runs", type=int, default=2)
+    ap.add_argument("--ignore-rows", default="0")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_loss: needs the GPU (there is no CPU path to time)")
@@ -42,11 +65,16 @@ def main():
     tg = tg.to(dev)
     g = torch.Generator(device=dev).manual_seed(9)
     outs = [torch.randn(args.batch, 18, args.size // s, args.size // s, args.nc + 6, generator=g, device=dev).requires_grad_() for s in (8, 16, 32)]
-    names = args.losses.split(",")
-    crits = {n: make_loss(n, m, HYP) for n in names}
+    rows = [int(v) for v in args.ignore_rows.split(",")]
+    names, crits, tables = [], {}, {}
+    for n in args.losses.split(","):
+        for r in rows:
+            key = n if r == 0 else "{}+{}rows".format(n, r)
+            names.append(key)
+            crits[key], tables[key] = make_loss(n, m, HYP), (ignore_table(r, args.batch, args.size, dev) if r else None)
 
-    def call(crit):
-        loss, _ = crit(outs, tg, sync_items=False)
+    def call(crit, ig):
+        loss, _ = crit(outs, tg, sync_items=False) if ig is None else crit(outs, tg, ignore=ig, sync_items=False)
         loss.backward()
         for o in outs:
             o.grad = None
@@ -55,18 +83,19 @@ def main():
     for _ in range(args.runs):
         for n in names:
             for _ in range(args.warmup):
-                call(crits[n])
+                call(crits[n], tables[n])
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record()
             for _ in range(args.iters):
-                call(crits[n])
+                call(crits[n], tables[n])
             t1.record()
             torch.cuda.synchronize()
             ms[n].append(round(t0.elapsed_time(t1) / args.iters, 4))
             crits[n].flush()
+    ignored = {n: [int(v) for v in crits[n].ignored_cells.tolist()] for n in names if tables[n] is not None}
     print(json.dumps({"what": "fused loss forward + backward, ms per call (device events)", "lib": os.path.basename(os.path.dirname(hip.LIB_PATH)) + "/" + os.path.basename(hip.LIB_PATH),
                       "batch": args.batch, "size": args.size, "nc": args.nc, "targets": int(tg.shape[0]), "iters": args.iters, "warmup": args.warmup,
-                      "ms_per_call": ms}))
+                      "ms_per_call": ms, "ignored_cells_per_scale": ignored}))
 
 
 if __name__ == "__main__":

@@ -8,7 +8,10 @@
   stages                         the first stage alone on one batch's table: the copy path (interp 2, with and without hsv) of
                                  ryolo_resize_hsv_windows against ryolo_resize_hsv_batch on the same bytes (GPU time, GB/s read + write),
                                  and ryolo_scene_label_rows
-usage: python tools/bench_scene_loader.py [batch] [size] [iters] [scenes] [out.json]  (default profiles/scene_loader_feed_rate.json)"""
+usage: python tools/bench_scene_loader.py [batch] [size] [iters] [scenes] [out.json]  (default profiles/scene_loader_feed_rate.json)
+       python tools/bench_scene_loader.py [batch] [size] [iters] [scenes] out.json ignore
+           only the scene_jitter loader, with ignore=None and with ignore=Ignore(0.1, True) (a tenth of the labels difficult), two runs
+           each, alternating: what the shadow table of the ignore rows costs per batch"""
 import json
 import os
 import random
@@ -103,6 +106,25 @@ def main():
         d = (rs.rand(nlab, 4, 2) - 0.5) * 60
         polys.append((c[:, None, :] + d).reshape(nlab, 8).astype(np.float32))
         labels.append(rs.randint(0, 16, size=nlab).astype(np.float32))
+    if len(sys.argv) > 6 and sys.argv[6] == "ignore":
+        from ryolov4_amd.datasets.scene_dataset import Ignore
+        diff = [(rs.rand(nlab) < 0.1).astype(np.uint8) for _ in range(nscene)]
+        res, rows = {}, 0
+        dss = {}
+        for name, ig in (("ignore_off", None), ("ignore_on", Ignore(0.1, True))):
+            dss[name] = SceneDataset(HYP, S, True, False, device=dev, overlap=S // 4, jitter=True, keep_empty=True, ignore=ig)
+            dss[name].set_arrays(scenes, polys, labels, difficult=diff)
+        for run in (1, 2):
+            for name, ds in dss.items():
+                res[f"{name}_run{run}"] = feed_rate(ds, B, iters, seed=run)
+                if ds.last_ignore is not None:
+                    rows = int(ds.last_ignore.shape[0])
+        out = {"what": f"scene loader feed rate with and without ignore rows, batch {B} at {S}x{S}, augment=True (mosaic 1.0, mixup 0.15, hsv, warp, flips), "
+                       f"{nscene} synthetic {side}x{side} scenes with {nlab} labels each, a tenth of them difficult; wall clock incl. host planning and "
+                       "the read-backs of the row counts", "result": res, "ignore_rows_of_the_last_batch": rows}
+        json.dump(out, open(sys.argv[5], "w"), indent=1)
+        print(json.dumps(out))
+        return
     res = {}
     sds = {}
     for name, jitter in (("scene_jitter", True), ("scene_planned", False)):
