@@ -625,7 +625,14 @@ int ryolo_tile_emit(const float* cand, const int64_t* order, const int32_t* num,
  * INTER_AREA forms, taps that straddle the scene border.  No intermediate cut is written.  The copy path (interp 2, NH = NW = c) moves 16
  * pixels per thread with 16-byte loads and stores, realigning the arbitrary source row start in registers; it never reads past the scene's
  * last byte.  dst_off multiples of 16 (what datasets/augment.py lays out) get the wide stores.  The copy path never consults c: an item with
- * interp 2 and (NH, NW) != (c, c) copies the NH x NW window at (x0, y0), with the same fill and the same bounds on every access. */
+ * interp 2 and (NH, NW) != (c, c) copies the NH x NW window at (x0, y0), with the same fill and the same bounds on every access.
+ * interp 3, the ROTATED CUT (the record ends in `double minv[6]`, read by this mode only): pixel (x, y) of the NH x NW result is
+ * cv::warpPerspective's INTER_LINEAR sample of the scene at (minv[0] x + minv[1] y + minv[2], minv[3] x + minv[4] y + minv[5]) with the
+ * constant border 114, then the hsv tables when lut >= 0: BIT-IDENTICAL to ryolo_warp_perspective_u8 on the whole scene (B = 1, Minv =
+ * {minv[0..5], 0, 0, 1}, border 114) followed by ryolo_hsv_gain_u8, and the sampler of ryolo_paste_pixels.  x0, y0, c are not read.  Items
+ * of all four modes may share one table and one launch.  A workgroup walks 64 x 16 tiles of the result, a thread owns 4 adjacent pixels
+ * and writes them as three dwords where the address allows (always with a dst_off multiple of 4 and NW a multiple of 4), bytes otherwise;
+ * no access leaves the scene or the NH NW 3 bytes of the result. */
 int ryolo_window_item_bytes(int* bytes);
 int ryolo_resize_hsv_windows(const uint8_t* pool, const void* items_dev, int nitems, int64_t max_pixels, const uint8_t* luts, uint8_t* stage,
                              ryolo_stream_t stream);

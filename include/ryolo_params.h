@@ -185,7 +185,8 @@ typedef struct ResizeItem {
     int interp, lut;
 } ResizeItem;
 
-/* ryolo_resize_hsv_windows: ResizeItem of the cut (its source size is c x c) + where the cut lies in which scene */
+/* ryolo_resize_hsv_windows: ResizeItem of the cut (its source size is c x c) + where the cut lies in which scene.  interp 3 = rotated cut:
+ * the NH x NW result is sampled from the scene through `minv` (the rule: include/ryolo.h); x0, y0, c are not read then. */
 typedef struct WindowItem {
     int64_t src_off, dst_off;    // byte offsets of the SCENE in the pool / of the result in the staging pool
     int SH, SW;                  // the scene
@@ -193,6 +194,7 @@ typedef struct WindowItem {
     int interp, lut;
     int x0, y0, c;               // the window, scene pixels; may hang over any border (x0, y0 < 0 included)
     int pad_;
+    double minv[6];              // interp 3 only: result pixel (x, y) -> scene pixel index (affine, row major 2 x 3)
 } WindowItem;
 
 /* ryolo_paste_prepare / _pixels / _labels: one pasted object */

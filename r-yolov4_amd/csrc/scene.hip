@@ -3,6 +3,7 @@
 // devkit (data/DOTA.yaml: data/DOTA/split/train) and has no code for this; the semantics are this project's, pinned by tests/scene_ref.py.
 //   resize_hsv_windows   ryolo_resize_hsv_batch (augment.hip) reading its source through a window: bit-identical to cutting the c x c window
 //                        first (114 wherever it lies outside the scene) and resizing the cut, without the pass that writes and re-reads the cut;
+//                        interp 3, the rotated cut: the result sampled from the scene through the item's affine map by warp_perspective's rule;
 //   scene_label_rows     which of the scene's labels belong to a window: shift by the window origin, intersection-over-foreground of the
 //                        quad with the window (Sutherland-Hodgman in fp64), rows below the threshold become NaN rows, which
 //                        label_stage_kernel carries and ryolo_encode_labels removes in order.
@@ -25,6 +26,52 @@ typedef scene_u32x4 scene_u32x4_a4 __attribute__((aligned(4)));        // a dwor
 
 #define SCENE_COPY_PX 16         // pixels per thread on the copy path: 48 bytes = three 16-byte stores
 
+// ---- rotated cut (interp 3): every pixel of the NH x NW result is warp_bilinear_px of the scene under the item's affine map, what
+// warp_perspective_kernel computes with Minv = {minv, 0, 0, 1}.  The workgroup walks 64 x 16 tiles of the result (16 x 16 threads of 4 adjacent
+// pixels), so that the source footprint of a turn is a compact rotated rectangle; a thread's 12 bytes go out as three dwords when they start
+// on a dword (dst 4-byte aligned and y NW + x a multiple of 4: every row when NW is one), byte by byte otherwise.  Inlined: the kernel
+// keeps its 72 VGPRs and stays without scratch (as a call it took 98 and 112 bytes of scratch per lane); the map's six doubles sit in SGPRs.
+#define SCENE_ROT_TW 64
+#define SCENE_ROT_TH 16
+__device__ __forceinline__ void rot_cut_item(const uint8_t* __restrict__ scene, const WindowItem& it, uint8_t* __restrict__ dst, bool hsv,
+                                             const uint8_t* slut, const int* divtab)
+{
+    const double m[9] = {it.minv[0], it.minv[1], it.minv[2], it.minv[3], it.minv[4], it.minv[5], 0.0, 0.0, 1.0};
+    const int NH = it.NH, NW = it.NW;
+    const unsigned tiles_x = ((unsigned)NW + SCENE_ROT_TW - 1) / SCENE_ROT_TW, tiles_y = ((unsigned)NH + SCENE_ROT_TH - 1) / SCENE_ROT_TH;
+    const unsigned ntiles = tiles_x * tiles_y;
+    const int tx = (threadIdx.x & 15) * 4, ty = threadIdx.x >> 4;
+    const bool dst_al = (((uintptr_t)dst) & 3) == 0;
+    for (unsigned tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const unsigned tyi = tile / tiles_x;
+        const int y = (int)tyi * SCENE_ROT_TH + ty, x = (int)(tile - tyi * tiles_x) * SCENE_ROT_TW + tx;
+        if (y >= NH || x >= NW) continue;
+        const int n = min(4, NW - x);
+        uint32_t w[3] = {0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (k < n) {
+                uint8_t d[3];
+                warp_bilinear_px(scene, it.SH, it.SW, m, x + k, y, SCENE_FILL, d);
+                int px[3] = {d[0], d[1], d[2]};
+                if (hsv) hsv_lut_pixel(px[0], px[1], px[2], slut, divtab);
+#pragma unroll
+                for (int ch = 0; ch < 3; ch++) { const int j = 3 * k + ch; w[j >> 2] |= (uint32_t)px[ch] << (8 * (j & 3)); }
+            }
+        }
+        const int64_t p0 = (int64_t)y * NW + x;
+        uint8_t* o = dst + p0 * 3;
+        if (dst_al && n == 4 && (p0 & 3) == 0) {
+            uint32_t* ov = reinterpret_cast<uint32_t*>(o);
+            ov[0] = w[0]; ov[1] = w[1]; ov[2] = w[2];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 12; j++)
+                if (j < 3 * n) o[j] = (uint8_t)((w[j >> 2] >> (8 * (j & 3))) & 255u);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void resize_hsv_windows_kernel(const uint8_t* __restrict__ pool, const WindowItem* __restrict__ items,
                                                                  const uint8_t* __restrict__ luts, uint8_t* __restrict__ stage)
 {
@@ -42,6 +89,11 @@ __global__ __launch_bounds__(256) void resize_hsv_windows_kernel(const uint8_t* 
     const uint8_t* scene = pool + it.src_off;
     uint8_t* dst = stage + it.dst_off;
     const int64_t scene_bytes = (int64_t)it.SH * it.SW * 3;
+
+    if (it.interp == 3) {                                           // (block-uniform, like the branches below)
+        rot_cut_item(scene, it, dst, it.lut >= 0, slut, divtab);
+        return;
+    }
 
     if (it.interp == 2) {
         // ---- copy (window == network size: every source use of a rates=(1.0,) dataset).  A thread owns 16 consecutive pixels of the result,

@@ -295,7 +295,7 @@ def warp_matrix(shape, a, s, tx, ty, border=(0, 0)):
 # the records of the device tables, as include/ryolo_params.h defines them (PasteRect, ResizeItem, WindowItem, PasteItem, LabelRow)
 _Rect, _ResizeItem, _WindowItem, _PasteItem, _LabelRow = (abi.STRUCTS[n] for n in ("PasteRect", "ResizeItem", "WindowItem", "PasteItem", "LabelRow"))
 LABEL_ROW_DTYPE, PASTE_ITEM_DTYPE = np.dtype(_LabelRow), np.dtype(_PasteItem)      # the same records for numpy: C offsets and itemsize
-INTERP_LINEAR, INTERP_AREA, INTERP_COPY = 0, 1, 2
+INTERP_LINEAR, INTERP_AREA, INTERP_COPY, INTERP_ROT = 0, 1, 2, 3
 _checked = False
 
 
@@ -375,21 +375,68 @@ def resize_hsv_batch(pool, items, luts=None):
 WINDOW_COORD_MAX = 1 << 24                # window origins and sides are exact as fp32 (the label shift) and far from int32 overflow
 
 
+def rot_window_maps(x0, y0, c, N, phi_deg):
+    """The two affine maps (float64 [6], row major 2 x 3) of the window (x0, y0, c) read at the angle phi_deg about its centre pixel
+    q = (x0 + k, y0 + k), k = (c - 1) / 2, into an N x N result (s = c / N):
+      minv  result pixel (u, v) -> scene pixel index: q + R (w), w = ((u + 0.5) s - 0.5 - k, (v + 0.5) s - 0.5 - k), R = [[cos, -sin], [sin, cos]]
+            (cv::resize's pixel-centre rule for the scale) — the `minv` of an INTERP_ROT item;
+      fwd   scene coordinate p -> the c x c window frame the label stage expects: R^T (p - q) + k.
+    cos and sin are exactly 0 / +-1 at multiples of 90 degrees: phi = 0 gives the translations x0 + u (at c = N) and p - (x0, y0), right
+    angles at c = N exact pixel permutations."""
+    c, N = int(c), int(N)
+    if c <= 0 or N <= 0:
+        raise ValueError(f"rot_window_maps: window side {c} and result side {N} must be positive")
+    phi = float(phi_deg)
+    if not math.isfinite(phi):
+        raise ValueError(f"rot_window_maps: angle {phi_deg!r}")
+    quarter = phi / 90.0
+    if quarter == math.floor(quarter):
+        cs, sn = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(quarter) % 4]
+    else:
+        cs, sn = math.cos(math.radians(phi)), math.sin(math.radians(phi))
+    s, k = c / N, (c - 1) / 2.0
+    qx, qy = x0 + k, y0 + k
+    t = 0.5 * s - 0.5 - k
+    minv = np.array([cs * s, -sn * s, qx + (cs - sn) * t, sn * s, cs * s, qy + (sn + cs) * t], dtype=np.float64)
+    fwd = np.array([cs, sn, k - (cs * qx + sn * qy), -sn, cs, k - (cs * qy - sn * qx)], dtype=np.float64)
+    return minv, fwd
+
+
+def map_polys(polys, fwd):
+    """polys [n, 8] through the affine map fwd (float64 [6]): float64 products and sums, left to right, rounded to float32 once."""
+    p = np.asarray(polys, dtype=np.float32).reshape(-1, 8).astype(np.float64)
+    x, y = p[:, 0::2], p[:, 1::2]
+    out = np.empty_like(p)
+    out[:, 0::2] = fwd[0] * x + fwd[1] * y + fwd[2]
+    out[:, 1::2] = fwd[3] * x + fwd[4] * y + fwd[5]
+    return out.astype(np.float32)
+
+
 def resize_hsv_windows(pool, items, luts=None):
     """resize_hsv_batch whose sources are WINDOWS of pool images: items [(pool image index, (x0, y0, c), (NH, NW), interp, lut index or -1)]
     -> (staging buffer, [byte offset of every result]).  Same bits as resize_hsv_batch on the c x c cut (114 where the window lies outside
-    its image), without the cut pass (csrc/scene.hip)."""
+    its image), without the cut pass (csrc/scene.hip).  An INTERP_ROT item, and no other, carries one more element behind its lut index:
+    `minv` (six floats: result pixel -> scene pixel index, rot_window_maps); its result is warp_perspective of the whole scene under that
+    map with border 114, then the tables.  The kernel does not read (x0, y0, c) of such an item; they describe the window, and the range
+    check below holds for them as for every item."""
     _check_layouts()
     dev = pool.buf.device
     arr = (_WindowItem * max(len(items), 1))()
     offs, total, maxpix = [], 0, 0
-    for k, (img, (x0, y0, c), (nh, nw), interp, lut) in enumerate(items):
+    for k, (img, (x0, y0, c), (nh, nw), interp, lut, *rest) in enumerate(items):
         sh, sw = pool.shapes[img]
         if not (0 < c <= 46340 and max(abs(x0), abs(y0)) < WINDOW_COORD_MAX and 0 < nh and 0 < nw):
             raise ValueError(f"resize_hsv_windows: window ({x0}, {y0}, {c}) -> {nh} x {nw} out of range")
         if interp == INTERP_COPY and (nh, nw) != (c, c):
             raise ValueError("resize_hsv_windows: a copied window keeps its size")
+        if len(rest) > 1 or (interp == INTERP_ROT) != (len(rest) == 1):
+            raise ValueError("resize_hsv_windows: an INTERP_ROT item, and no other, carries minv behind its lut index")
         arr[k] = _WindowItem(pool.offsets[img], total, sh, sw, nh, nw, interp, lut, x0, y0, c, 0)
+        if rest:
+            minv = np.asarray(rest[0], dtype=np.float64).reshape(-1)
+            if minv.shape != (6,) or not np.isfinite(minv).all():
+                raise ValueError("resize_hsv_windows: minv is six finite numbers")
+            arr[k].minv[:] = minv.tolist()
         offs.append(total)
         total += ((nh * nw * 3 + 15) // 16) * 16
         maxpix = max(maxpix, nh * nw)

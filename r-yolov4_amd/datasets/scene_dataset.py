@@ -134,6 +134,69 @@ def check_ignore(ignore, iof_thr):
     return ignore
 
 
+class Rotate:
+    """Rotation augmentation of window training (SceneDataset(rotate=...)): a use's window is read from the scene at a random angle about its
+    centre pixel (INTERP_ROT of ryolo_resize_hsv_windows), so the corners of the result hold scene pixels — and the scene's labels under
+    the same map — instead of the fill that hyp["rotate"] leaves when it turns a finished canvas.  Per use one coin from a private
+    random.Random(seed); under `p` one angle uniform in [-degrees, degrees]; with step > 0 it becomes k * step, k the nearest integer to
+    angle / step (Python's round: halves to even) clamped to |k| <= floor(degrees / step), so a snapped angle never leaves the range.
+    Off by default; the effect on DOTA mAP has not been measured."""
+    __slots__ = ("degrees", "p", "step", "seed", "_rng")
+
+    def __init__(self, degrees=180.0, p=0.5, step=0.0, seed=0):
+        for name, v in (("degrees", degrees), ("p", p), ("step", step)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or v < 0:
+                raise ValueError(f"Rotate: {name} must be a finite number >= 0, got {v!r}")
+        if p > 1:
+            raise ValueError(f"Rotate: p is a probability, got {p!r}")
+        self.degrees, self.p, self.step, self.seed = float(degrees), float(p), float(step), seed
+        self._rng = _py_random.Random(seed)
+
+    def draw(self):
+        """The angle of one use in degrees, or None for an unrotated use.  Draw order: the coin, then the angle if the coin is under p."""
+        if not self._rng.random() < self.p:
+            return None
+        a = self._rng.uniform(-self.degrees, self.degrees)
+        if self.step > 0:
+            kmax = math.floor(self.degrees / self.step)
+            a = max(-kmax, min(kmax, round(a / self.step))) * self.step
+        return a
+
+    def __repr__(self):
+        return f"Rotate(degrees={self.degrees}, p={self.p}, step={self.step}, seed={self.seed!r})"
+
+
+def check_rotate(rotate, augment):
+    """-> None or a Rotate with a generator of its own at the start of its seed; a dict of Rotate's arguments is accepted."""
+    if rotate is None:
+        return None
+    if isinstance(rotate, dict):
+        try:
+            rotate = Rotate(**rotate)
+        except TypeError as e:
+            raise ValueError(f"rotate: {e}") from None
+    elif isinstance(rotate, Rotate):
+        rotate = Rotate(rotate.degrees, rotate.p, rotate.step, rotate.seed)
+    else:
+        raise ValueError(f"rotate must be None, a Rotate or a dict of its arguments, got {rotate!r}")
+    if not augment:
+        raise ValueError("SceneDataset: rotate is an augmentation (augment=True); validation and label_table() read the planned windows")
+    return rotate
+
+
+def rot_window_box(x0, y0, c, phi_deg):
+    """(xlo, xhi, ylo, yhi): the axis-aligned bounding box, in scene coordinates, of the window frame [0, c]^2 of a use rotated by phi_deg
+    (the corners through the inverse of rot_window_maps' fwd)."""
+    _, f = A.rot_window_maps(x0, y0, c, c, phi_deg)
+    k = (c - 1) / 2.0
+    xs, ys = [], []
+    for u in (0.0, float(c)):
+        for v in (0.0, float(c)):
+            xs.append(x0 + k + f[0] * (u - k) - f[1] * (v - k))                 # q + R (corner - k), R = fwd's rotation transposed
+            ys.append(y0 + k + f[1] * (u - k) + f[0] * (v - k))
+    return min(xs), max(xs), min(ys), max(ys)
+
+
 class SceneDataset(BaseDataset):
     """BaseDataset whose items are windows of scenes.  Subclasses fill `scene_files` / `scene_label_files`, implement `load_files` and call
     `plan_windows()`; `set_arrays(scenes, polys, labels)` does the same from decoded scenes.  `img_files` / `label_files` / `len()` are per
@@ -158,10 +221,20 @@ class SceneDataset(BaseDataset):
     small uploads, a few element-wise torch operations and one host read (the row count) per batch.  The windows, every draw from `rng`,
     copy-paste (pastes neither bury ignore rows nor count them for occ_thr), keep_empty and label_table() are what they are without it.
     Not covered: rows that the centre filter of ryolo_encode_labels drops on the plain DOTADataset path, and ignore rows of a mixup
-    partner beyond carrying its slot."""
+    partner beyond carrying its slot.
+
+    rotate (a Rotate or a dict of its arguments; default None: off, not one draw or launch more; augment only): after the jitter draw every
+    use draws a coin and, under p, an angle from Rotate's private generator; a rotated use is read from the scene through
+    augment.rot_window_maps' pixel map (INTERP_ROT, the same row of the same table; about the window's centre pixel, 114 beyond the
+    scene), and its labels are the scene's under the label map: the polygons the cull against the rotated window's bounding box keeps are
+    mapped on the host in float64 and tested by ryolo_scene_label_rows against the window (0, 0, c) — in the main table and in the shadow
+    table of `ignore` alike.  `last_angles`: degrees, or None for an unrotated use, per row of `last_windows`.  Unrotated uses, `rng`, the
+    jitter generator, copy-paste, keep_empty and label_table() (planned, unrotated windows) are what they are without it.  Not built:
+    keeping the rotated window inside the scene, keeping the p_object label inside the rotated window, area filtering for c > img_size
+    (rotated cuts are bilinear, as load_image's resizes under augment are).  tests/scene_rotate_ref.py restates it."""
 
     def __init__(self, hyp, img_size, augment, csl, normalized_labels=False, overlap=200, rates=(1.0,), iof_thr=0.7, keep_empty=False,
-                 jitter=None, p_object=0.5, window_seed=0, copy_paste=None, ignore=None, **device_kw):
+                 jitter=None, p_object=0.5, window_seed=0, copy_paste=None, ignore=None, rotate=None, **device_kw):
         super().__init__(hyp, img_size, augment, csl, normalized_labels, **device_kw)
         if normalized_labels:
             raise ValueError("SceneDataset: scene labels are in scene pixels (normalized_labels=False)")
@@ -171,6 +244,7 @@ class SceneDataset(BaseDataset):
             raise ValueError(f"SceneDataset: p_object is a probability, got {p_object}")
         scene_windows(1, 1, img_size, overlap, rates)               # argument errors now, not at the first scene
         self.ignore = check_ignore(ignore, iof_thr)
+        self.rotate = check_rotate(rotate, augment)
         self.last_ignore = self._ignore_pending = None
         self._shadow = {}                                          # resize-table row -> (polys, classes, difficult flags) the cull handed to that use
         self.overlap, self.rates, self.iof_thr, self.keep_empty = overlap, tuple(rates), float(iof_thr), bool(keep_empty)
@@ -180,6 +254,8 @@ class SceneDataset(BaseDataset):
         self.scene_files, self.scene_label_files = [], []
         self.items = []                                            # (scene, rate index, x0, y0, c)
         self.last_windows, self._row_wins = [], []
+        self.last_angles, self._maps = [], {}                      # degrees or None per resize-table row; row -> (minv, fwd) of a rotated use
+        self._rotating = True                                      # (off while label_table() reads the planned windows)
         self._boxes = {}                                           # scene -> label_boxes of its labels (the cull of every use)
         self._difficult = {}                                       # scene -> uint8 [n] "difficult" flags (scene_difficult)
         if copy_paste is not None and not isinstance(copy_paste, CopyPaste):
@@ -295,16 +371,43 @@ class SceneDataset(BaseDataset):
         if row != len(self.last_windows):
             raise RuntimeError("SceneDataset: resize table and window table out of step")
         self.last_windows.append((index, s, x0, y0, c))
+        self.last_angles.append(self.rotate.draw() if self.rotate is not None and self._rotating else None)
         return c, c
 
-    def _use_labels(self, index, row):
+    def _label_wins(self):
+        """The windows ryolo_scene_label_rows tests the rows of each use against: (x0, y0, c), and (0, 0, c) for a rotated use, whose
+        polygons the host has already mapped into the window frame."""
+        return [(0, 0, w[4]) if a is not None else w[2:] for w, a in zip(self.last_windows, self.last_angles)]
+
+    def _use_cull(self, row):
+        """(indices the host cull keeps, their polygons, their classes) for the use `row`, in file order.  Unrotated: bounding boxes against
+        the window, polygons in scene pixels.  Rotated: bounding boxes against the bounding box of the rotated window (a superset of what
+        can have a share inside it), polygons mapped into the window frame by rot_window_maps' fwd in float64."""
         _, s, x0, y0, c = self.last_windows[row]
-        if self.ignore is None:
-            polys, cls = self._window_labels(s, x0, y0, c)
-        else:
-            # the shadow of this use: everything the cull kept, difficult labels included; with Ignore.difficult those are no targets
+        polys, cls = self.scene_labels(s)
+        if self.last_angles[row] is None:
             keep = self._window_cull(s, x0, y0, c)
-            polys, cls = (v[keep] for v in self.scene_labels(s))
+            return keep, polys[keep], cls[keep]
+        boxes = self._boxes.get(s)
+        if boxes is None:
+            boxes = self._boxes[s] = label_boxes(polys)
+        xlo, xhi, ylo, yhi = rot_window_box(x0, y0, c, self.last_angles[row])
+        keep = np.nonzero((boxes[1] > xlo - 1e-3) & (boxes[0] < xhi + 1e-3) & (boxes[3] > ylo - 1e-3) & (boxes[2] < yhi + 1e-3))[0]
+        return keep, A.map_polys(polys[keep], self._use_maps(row)[1]), cls[keep]
+
+    def _use_maps(self, row):
+        got = self._maps.get(row)
+        if got is None:
+            _, _, x0, y0, c = self.last_windows[row]
+            _, (n, _) = self._resized(c, c)
+            got = self._maps[row] = A.rot_window_maps(x0, y0, c, n, self.last_angles[row])
+        return got
+
+    def _use_labels(self, index, row):
+        s = self.last_windows[row][1]
+        keep, polys, cls = self._use_cull(row)
+        if self.ignore is not None:
+            # the shadow of this use: everything the cull kept, difficult labels included; with Ignore.difficult those are no targets
             diff = self.scene_difficult(s)[keep]
             self._shadow[row] = (polys, cls, diff)
             if self.ignore.difficult:
@@ -314,16 +417,20 @@ class SceneDataset(BaseDataset):
 
     def _pixel_stage(self, pool, items, luts):
         pool.ensure(w[1] for w in self.last_windows)
-        return A.resize_hsv_windows(pool, [(s, (x0, y0, c), hw, interp, lut) for (_, s, x0, y0, c), (_, hw, interp, lut) in zip(self.last_windows, items)],
-                                    luts)
+        table = [(s, (x0, y0, c), hw, interp, lut) for (_, s, x0, y0, c), (_, hw, interp, lut) in zip(self.last_windows, items)]
+        for row, a in enumerate(self.last_angles):
+            if a is not None:                                       # a rotated use: the same row of the same table, read through its map
+                table[row] = table[row][:3] + (A.INTERP_ROT, table[row][4], self._use_maps(row)[0])
+        return A.resize_hsv_windows(pool, table, luts)
 
     def _label_table(self, rows):
         table = super()._label_table(rows)
-        A.scene_label_rows(table, len(rows), np.concatenate(self._row_wins), [w[2:] for w in self.last_windows], self.iof_thr)
+        A.scene_label_rows(table, len(rows), np.concatenate(self._row_wins), self._label_wins(), self.iof_thr)
         return table
 
     def assemble_batch(self, indices):
         self.last_windows, self._row_wins, self._shadow = [], [], {}
+        self.last_angles, self._maps = [], {}
         self.last_ignore = self._ignore_pending = None
         batch = super().assemble_batch(indices)
         if self._ignore_pending is not None:
@@ -353,7 +460,7 @@ class SceneDataset(BaseDataset):
             self.last_ignore = torch.empty((0, 9), dtype=torch.float32, device=dev)
             return
         table = A.upload_label_rows(rows, dev)
-        iof = A.scene_label_rows(table, n, np.concatenate(wins), [w[2:] for w in self.last_windows], ig.iof_lo, want_iof=True)
+        iof = A.scene_label_rows(table, n, np.concatenate(wins), self._label_wins(), ig.iof_lo, want_iof=True)
         t10 = A.label_stage_table(table, n, mats, dev)              # (slot, class, 8 vertices in canvas pixels; NaN: below iof_lo or filtered)
         quad = t10[:, 2:10]
         sel = iof < self.iof_thr
@@ -408,12 +515,13 @@ class SceneDataset(BaseDataset):
     def _label_chunk(self, indices):
         """BaseDataset._label_chunk over the PLANNED windows: jitter is off for its duration (the window generator is not touched) and the
         window tables of the last batch are put back afterwards."""
-        saved = self.jitter, self.last_windows, self._row_wins, self.ignore
+        saved = self.jitter, self.last_windows, self._row_wins, self.ignore, self.last_angles, self._maps, self._rotating
         self.jitter, self.last_windows, self._row_wins, self.ignore = False, [], [], None       # (the table holds every target: no ignore rows here)
+        self.last_angles, self._maps, self._rotating = [], {}, False                            # (nor a rotated use: no angle is drawn)
         try:
             return super()._label_chunk(indices)
         finally:
-            self.jitter, self.last_windows, self._row_wins, self.ignore = saved
+            self.jitter, self.last_windows, self._row_wins, self.ignore, self.last_angles, self._maps, self._rotating = saved
 
 
 class DOTASceneDataset(SceneDataset):

@@ -11,7 +11,8 @@ under the current training step), `rank` / `world_size` (data parallel: each ran
 `dataset_type="DOTA_scenes"` (this project's, not the reference's): `data_dir` holds FULL-SIZE scenes in the DOTA layout and the windows
 are cut on the device (datasets/scene_dataset.py); its keywords `overlap`, `rates`, `iof_thr`, `keep_empty`, `jitter`, `p_object`,
 `window_seed`, `copy_paste` (datasets/copy_paste.py), `ignore` (an Ignore of datasets/scene_dataset.py or a dict of its arguments: the batch's
-ignore rows in `dataset.last_ignore`, for the criterion's `ignore` argument) pass through."""
+ignore rows in `dataset.last_ignore`, for the criterion's `ignore` argument), `rotate` (a Rotate of datasets/scene_dataset.py or a dict of
+its arguments: with augment, windows read from the scene at a random angle) pass through."""
 from ..datasets.base_dataset import DeviceLoader
 from ..datasets.DOTA_dataset import DOTADataset
 from ..datasets.scene_dataset import DOTASceneDataset

@@ -11,7 +11,10 @@
 usage: python tools/bench_scene_loader.py [batch] [size] [iters] [scenes] [out.json]  (default profiles/scene_loader_feed_rate.json)
        python tools/bench_scene_loader.py [batch] [size] [iters] [scenes] out.json ignore
            only the scene_jitter loader, with ignore=None and with ignore=Ignore(0.1, True) (a tenth of the labels difficult), two runs
-           each, alternating: what the shadow table of the ignore rows costs per batch"""
+           each, alternating: what the shadow table of the ignore rows costs per batch
+       python tools/bench_scene_loader.py [batch] [size] [iters] [scenes] out.json rotate
+           the scene_jitter loader with rotate=None and with Rotate(degrees=180, p=1), two runs each, alternating, the host time in the
+           hooks, and one launch of the window stage over a batch of windows copied against the same windows read at an angle"""
 import json
 import os
 import random
@@ -122,6 +125,47 @@ def main():
         out = {"what": f"scene loader feed rate with and without ignore rows, batch {B} at {S}x{S}, augment=True (mosaic 1.0, mixup 0.15, hsv, warp, flips), "
                        f"{nscene} synthetic {side}x{side} scenes with {nlab} labels each, a tenth of them difficult; wall clock incl. host planning and "
                        "the read-backs of the row counts", "result": res, "ignore_rows_of_the_last_batch": rows}
+        json.dump(out, open(sys.argv[5], "w"), indent=1)
+        print(json.dumps(out))
+        return
+    if len(sys.argv) > 6 and sys.argv[6] == "rotate":
+        from ryolov4_amd.datasets.scene_dataset import Rotate
+        res, dss = {}, {}
+        for name, rot in (("rotate_off", None), ("rotate_on", Rotate(degrees=180.0, p=1.0))):
+            dss[name] = SceneDataset(HYP, S, True, False, device=dev, overlap=S // 4, jitter=True, keep_empty=True, rotate=rot)
+            dss[name].set_arrays(scenes, polys, labels)
+        for run in (1, 2):
+            for name, ds in dss.items():
+                res[f"{name}_run{run}"] = feed_rate(ds, B, iters, seed=run)
+        host = {name: hook_ms(ds, B, iters) for name, ds in dss.items()}
+        # the window stage alone: B windows of the last rotated batch, copied and read at their drawn angles (tables uploaded once)
+        ds = dss["rotate_on"]
+        wins, angles = list(ds.last_windows)[:B], list(ds.last_angles)[:B]
+        ds._pool.ensure(range(nscene))
+        stages = {"items": len(wins)}
+        for tag, lut in (("plain", -1), ("hsv", 0)):
+            ltd = None if lut < 0 else A._to_device(np.ascontiguousarray(A.hsv_luts(np.asarray([1.01, 1.3, 0.8])), dtype=np.uint8), dev)
+            for mode in ("copied", "rotated"):
+                arr = (A._WindowItem * len(wins))()
+                total = 0
+                for k, ((_, s, x0, y0, c), a) in enumerate(zip(wins, angles)):
+                    sh, sw = ds._pool.shapes[s]
+                    arr[k] = A._WindowItem(ds._pool.offsets[s], total, sh, sw, c, c, A.INTERP_COPY if mode == "copied" else A.INTERP_ROT, lut, x0, y0, c, 0)
+                    if mode == "rotated":
+                        arr[k].minv[:] = A.rot_window_maps(x0, y0, c, c, a)[0].tolist()
+                    total += ((c * c * 3 + 15) // 16) * 16
+                tab = A._to_device(arr, dev)
+                stage = torch.empty(total, dtype=torch.uint8, device=dev)
+                ms = gpu_ms(lambda: hip.call("ryolo_resize_hsv_windows", hip.ptr(ds._pool.buf), hip.ptr(tab), len(wins), S * S, hip.ptr(ltd), hip.ptr(stage),
+                                             hip.stream()))
+                nbytes = sum(w[4] * w[4] * 3 for w in wins)
+                stages[f"{mode}_{tag}"] = {"ms": round(ms, 3), "MB_written": round(nbytes / 1e6, 1), "GBps_read_plus_written": round(2 * nbytes / ms / 1e6, 1)}
+        out = {"what": f"scene loader feed rate with rotate=None and Rotate(degrees=180, p=1), batch {B} at {S}x{S}, augment=True (mosaic 1.0, mixup 0.15, hsv, "
+                       f"warp, flips), {nscene} synthetic {side}x{side} scenes with {nlab} labels each, two runs each, alternating; wall clock incl. host "
+                       "planning and the count read-back; host_ms_in_hooks as in the default leg; stages: one launch of ryolo_resize_hsv_windows over "
+                       f"{len(wins)} windows of the last batch, copied (interp 2) and rotated (interp 3, the drawn angles), device events, 10 launches; "
+                       "GB/s counts the result bytes twice (a rotated read touches up to 4 source pixels per result pixel, mostly from cache)",
+               "result": res, "host_ms_in_hooks": host, "stages": stages}
         json.dump(out, open(sys.argv[5], "w"), indent=1)
         print(json.dumps(out))
         return
